@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - edges/sec (fwd+bwd) of the MMA message-passing hot path on MI355X, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2l]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2l] [--full] [--dump-outputs DIR]
 
 N > 1 without a launcher (RANK unset): bench.py starts N child ranks itself (`python -m torch.distributed.run ...
 bench.py <same args>`) BEFORE anything touches the GPU, relays rank 0's JSON line and exits with the children's status.
@@ -24,6 +24,11 @@ timed region) and `cpu_baseline` (the CPU oracle on a bounded sample).  The verb
 every timed call), `plan_build`, `ranks` (N > 1) and `extra`, the other BASELINE configs that fit one GPU (C1, C3, C2, C2L: layer
 fwd+bwd, eager and one-hipGraph replay; C5 at its per-GPU shard shape) - goes to stderr as one `{"detail": ...}` line and to
 $MMA_BENCH_DETAIL (default gpurun_out/bench_detail.json); the compact line keeps `kernels_ms` and `extra_summary`.
+
+A plain run sets up, warms up, times the --steps steps and prints the line: `roofline` and `kernels` come from the HIP events of
+those steps.  Everything that takes work of its own - `cpu_baseline`, `plan_build`, `extra`, and at N > 1 the default --verify
+check and the instrumented exchange pass - runs only with --full.  --dump-outputs DIR writes what the last timed step computed
+(forward output and dL/dx on a fixed sample of rows, every parameter gradient) as DIR/<name>.npy, float32 (dump_outputs).
 
 Byte counts.  `roofline.achieved` = `algorithmic_bytes()` of THIS kernel / its HIP-event time: the bytes the kernel's design has to
 move with zero credit for cache reuse of gathered rows.  For K1 that is SURVEY 8d's B_fwd.  For the backward it is
@@ -440,7 +445,12 @@ def gr_setup(n_graphs, dev, seed=0, categorical=False):
         x.grad = None
         for q in params:                   # optimizer.zero_grad(): the backward then assigns instead of launching an add per tensor
             q.grad = None
-        conv(x, eig, ea).backward(cot)
+        out = conv(x, eig, ea)
+        out.backward(cot)
+        if step.last is not None:
+            step.last["out"] = out
+    step.last = None                  # bench.py --dump-outputs sets a dict: the forward output of the last call
+    step.x = x
 
     def check():          # outside every timed region: the long-segment list of the layer's CSR was never found clobbered (K3 / K4 skip such a list and flag it)
         from mma_amd import functional as Fn
@@ -778,6 +788,32 @@ def emit(line, detail):
     print(out, flush=True)
 
 
+DUMP_ROWS = 32768           # rows of each per-node output kept by --dump-outputs
+DUMP_LIMIT = 64 << 20       # bytes of all the files of one dump
+
+
+def dump_outputs(path, per_row, whole):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as <path>/<name>.npy in float32.  `per_row`
+    ((rows, ...) tensors: forward output, dL/dx) keeps a fixed sample of DUMP_ROWS rows, the same for every run of the same
+    arguments (their indices in sample_rows.npy, float64); `whole` (parameter gradients) is written as it is."""
+    os.makedirs(path, exist_ok=True)
+    n = {t.shape[0] for t in per_row.values()}
+    assert len(n) == 1, n
+    n = n.pop()
+    rows = np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_ROWS), replace=False))
+    arrays = {"sample_rows": rows.astype(np.float64)}
+    idx = torch.from_numpy(rows)
+    for name, t in per_row.items():
+        arrays[name] = t.detach()[idx.to(t.device)].float().cpu().numpy()
+    for name, t in whole.items():
+        if t.grad is not None:
+            arrays["grad_" + name.replace(".", "_")] = t.grad.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, "--dump-outputs: %d bytes > %d" % (total, DUMP_LIMIT)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _compact_roofline(roof):
     keep = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "traffic_source", "algorithmic_bytes", "frac_rocprof")
     r = {k: roof.get(k) for k in keep}
@@ -829,12 +865,15 @@ def main():
     ap.add_argument("--force-sharded", action="store_true", help="use the sharded (RCCL) path even at world size 1")
     ap.add_argument("--verify", dest="verify", action="store_true", default=None, help="before timing, check the sharded layer against the "
                     "unsharded one on a 2^14-node R-MAT (rank 0 computes both; forward, dL/dx, parameter gradients) and exit non-zero on "
-                    "mismatch: the default whenever the sharded path runs on more than one rank")
+                    "mismatch: with --full, the check (non-fatal) is the default whenever the sharded path runs on more than one rank")
     ap.add_argument("--no-verify", dest="verify", action="store_false")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend; 'gloo' (halo staged through the host) lets "
                     "several ranks share one GPU to rehearse the N>1 path on a 1-GPU box")
-    ap.add_argument("--cpu-sample", type=int, default=150000, help="target nodes in the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary configurations (C1, C3, C2, C2L) and the loop baseline")
+    ap.add_argument("--full", action="store_true", help="beyond the headline: the CPU baselines, the plan-build timings, the secondary "
+                    "configurations, and at N > 1 the default --verify check and the instrumented exchange pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--cpu-sample", type=int, default=150000, help="--full: target nodes in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the secondary configurations (C1, C3, C2, C2L) and the loop baseline")
     ap.add_argument("--rendezvous-only", action="store_true", help="(tests) ranks meet, all-reduce their rank and leave: "
                     "checks the launch path without a GPU")
     args = ap.parse_args()
@@ -908,22 +947,25 @@ def main():
                     compound_scalers=True) if args.true_degree_scalers else {}
 
     plan_build = None
+    last = {}               # --dump-outputs: the forward output of the last step
     if not sharded:
         # the graph plan (CSR, transposed CSR, work items, hub lists; the tail SpMM's plan): built on the DEVICE (K6 radix sorts + scans,
         # NCGraph.from_device_csr) - the host numpy builder of round 2 is timed beside it
         rp_d, cl_d = torch.from_numpy(np.ascontiguousarray(rowptr)).to(dev), torch.from_numpy(np.ascontiguousarray(col)).to(dev)
-        mma_amd.NCGraph.from_device_csr(rp_d, cl_d, H=H)                       # warm-up (allocator, rocPRIM temporary sizes)
-        torch.cuda.synchronize(); t0 = time.perf_counter()
+        if args.full:
+            mma_amd.NCGraph.from_device_csr(rp_d, cl_d, H=H)                   # warm-up (allocator, rocPRIM temporary sizes)
+            torch.cuda.synchronize(); t0 = time.perf_counter()
         graph = mma_amd.NCGraph.from_device_csr(rp_d, cl_d, H=H)
         adj = mma_amd.graph.SpmmGraph.from_device_csr(rp_d, cl_d)
-        torch.cuda.synchronize(); t_dev = time.perf_counter() - t0
-        plan_build = {"device_s": t_dev, "what": "NCGraph + SpmmGraph plans of the whole graph from a device-resident CSR"}
-        if args.cpu_sample:
-            t0 = time.perf_counter()
-            mma_amd.NCGraph(rowptr, col, dev, H=H)
-            dst = np.repeat(np.arange(N, dtype=np.int64), np.diff(rowptr))
-            mma_amd.graph.SpmmGraph(dst, col, None, N, N, dev)
-            torch.cuda.synchronize(); plan_build["numpy_s"] = time.perf_counter() - t0
+        if args.full:
+            torch.cuda.synchronize(); t_dev = time.perf_counter() - t0
+            plan_build = {"device_s": t_dev, "what": "NCGraph + SpmmGraph plans of the whole graph from a device-resident CSR"}
+            if args.cpu_sample:
+                t0 = time.perf_counter()
+                mma_amd.NCGraph(rowptr, col, dev, H=H)
+                dst = np.repeat(np.arange(N, dtype=np.int64), np.diff(rowptr))
+                mma_amd.graph.SpmmGraph(dst, col, None, N, N, dev)
+                torch.cuda.synchronize(); plan_build["numpy_s"] = time.perf_counter() - t0
         layer = make_layer(mma_amd, graph, H, C, names, args.dropout, dev, **extra_kw)
         x = torch.from_numpy(feature_rows(0, N, H, 42)).to(dev).requires_grad_(True)
         cot = torch.from_numpy(feature_rows(0, N, C, 43, relu=False)).to(dev)
@@ -934,11 +976,14 @@ def main():
                 prm.grad = None
             out = layer(x, adj)
             out.backward(cot)
+            if args.dump_outputs:
+                last["out"] = out
         local_edges, n_local = E, N
+        params = [("weight", layer.weight), ("bias", layer.bias)] + [("mask_" + n, getattr(layer, "mask_" + n)) for n in names]
     else:
         from mma_amd.sharded import EXCHANGE_LOG, ShardedMMA
         verify = None
-        if args.verify or (args.verify is None and world > 1):
+        if args.verify or (args.verify is None and world > 1 and args.full):
             # asked for (--verify): a mismatch ends the run (exit 3).  By default at N > 1: the check runs and its verdict travels in the
             # line, but a mismatch does not throw the measurement away - the first multi-GPU run happens where nobody can re-run it
             verify = verify_sharded(rank, world, dev, args.backend, H, C, names, args.dropout, extra_kw, fatal=bool(args.verify))
@@ -953,7 +998,10 @@ def main():
             out = sh(x)
             out.backward(cot)
             sh.allreduce_grads()
+            if args.dump_outputs:
+                last["out"] = out
         local_edges, n_local = sh.local_edges, sh.hi - sh.lo
+        params = [("weight", sh.weight), ("bias", sh.bias)] + [("mask_" + n, sh.masks[n]) for n in names]
         barrier()
         if rank == 0 and shm_tag:
             for suf in ("_rowptr.npy", "_col.npy"):
@@ -978,23 +1026,27 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     timer.enabled = False
+    if args.dump_outputs and rank == 0:      # at N > 1: rank 0's rows, and the parameter gradients after their all-reduce
+        dump_outputs(args.dump_outputs, {"out": last["out"], "grad_x": x.grad}, dict(params))
     ranks = None
     dt_own = dt
     if sharded:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
-        # exchange_ms: a SEPARATE short instrumented pass (side-stream work.wait() + two events per exchange), never the headline's path
-        n_inst = max(1, min(args.steps, 3))
-        counts = (EXCHANGE_LOG.bytes_sent, EXCHANGE_LOG.bytes_received, EXCHANGE_LOG.calls)
-        EXCHANGE_LOG.timed = True
-        for _ in range(n_inst):
-            step()
-        barrier()
         dt_own = own_start.elapsed_time(own_end) * 1e-3
-        EXCHANGE_LOG.timed = False
-        exchange_ms_inst = EXCHANGE_LOG.exchange_ms() / n_inst
-        EXCHANGE_LOG.bytes_sent, EXCHANGE_LOG.bytes_received, EXCHANGE_LOG.calls = counts
+        exchange_ms_inst = None
+        if args.full:
+            # exchange_ms: a SEPARATE short instrumented pass (side-stream work.wait() + two events per exchange), never the headline's path
+            n_inst = max(1, min(args.steps, 3))
+            counts = (EXCHANGE_LOG.bytes_sent, EXCHANGE_LOG.bytes_received, EXCHANGE_LOG.calls)
+            EXCHANGE_LOG.timed = True
+            for _ in range(n_inst):
+                step()
+            barrier()
+            EXCHANGE_LOG.timed = False
+            exchange_ms_inst = EXCHANGE_LOG.exchange_ms() / n_inst
+            EXCHANGE_LOG.bytes_sent, EXCHANGE_LOG.bytes_received, EXCHANGE_LOG.calls = counts
 
     spans = timer.summary()
     if sharded:
@@ -1047,7 +1099,7 @@ def main():
         label = "C4" if is_c4 else ("C5" if is_c5 else "custom (not a BASELINE config)")
         cpu = None
         extra = None
-        if not sharded:
+        if args.full and not sharded:
             if args.cpu_sample:
                 cpu = cpu_baseline(rowptr, col, H, names, "new_sigmoid", args.dropout, min(args.cpu_sample, N), 42,
                                    "%s R-MAT" % label.split()[0])
@@ -1095,6 +1147,8 @@ def run_c2l(args, dev, rank=0, world=1, barrier=None):
     from mma_amd import functional as Fn
     from mma_amd.sharded import allreduce_grads
     conv, fwd_bwd, N, E = gr_setup(args.molecules, dev, seed=rank)
+    if args.dump_outputs:
+        fwd_bwd.last = {}
     params = [q for q in conv.parameters() if q.requires_grad]
     if world > 1:
         with torch.no_grad():                                   # replicas start from rank 0's parameters
@@ -1121,6 +1175,9 @@ def run_c2l(args, dev, rank=0, world=1, barrier=None):
     barrier()
     dt = time.perf_counter() - t0
     timer.enabled = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"out": fwd_bwd.last["out"], "grad_x": fwd_bwd.x.grad},
+                     {n: q for n, q in conv.named_parameters() if q.requires_grad})
     fwd_bwd.check()
     tot = torch.tensor([float(E), float(N)], dtype=torch.float64)
     if world > 1:
@@ -1147,7 +1204,7 @@ def run_c2l(args, dev, rank=0, world=1, barrier=None):
                     "frac_rocprof": (ab[n] / (rocprof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if rocprof_ms else None}
     dom = max(roofs, key=lambda n: kernels[n]["avg_ms"])
     cpu = None
-    if args.cpu_sample and world == 1:
+    if args.full and args.cpu_sample and world == 1:
         cpu = gr_cpu_baseline(200)
     line = {"metric": "aggregated edges/sec (fwd+bwd) MultiMaskConv", "value": E_all * args.steps / dt, "unit": "edges/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,

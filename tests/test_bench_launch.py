@@ -64,3 +64,26 @@ def test_metric_line_is_compact_and_strict_json(capsys, tmp_path, monkeypatch):
     det = strict_loads([l for l in cap.err.splitlines() if l.startswith('{"detail"')][0])["detail"]
     assert det["extra"]["C3"]["ms_per_step_hipgraph"] is None and len(det["kernels"]) == 40            # inf -> null, nothing dropped
     assert strict_loads(open(tmp_path / "d" / "detail.json").read())["detail"]["metric"] == d["metric"]
+
+
+def test_dump_outputs_writes_a_fixed_row_sample_in_float32(tmp_path):
+    """--dump-outputs: per-node outputs on the same seeded row sample in every run, parameter gradients whole, float32 / float64 only,
+    within the size limit; a parameter without a gradient is left out."""
+    import numpy as np
+    import torch
+    import bench
+    n = bench.DUMP_ROWS + 1000
+    out, gx = torch.randn(n, 16), torch.randn(n, 64)
+    w = torch.nn.Parameter(torch.randn(64, 16)); w.grad = torch.randn(64, 16)
+    b = torch.nn.Parameter(torch.randn(16))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"out": out, "grad_x": gx}, {"weight": w, "lin.bias": b})
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["grad_weight.npy", "grad_x.npy", "out.npy", "sample_rows.npy"]
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == bench.DUMP_ROWS and len(np.unique(rows)) == len(rows) and rows.max() < n
+    for f in files:
+        a, c = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, c), f
+    assert np.array_equal(np.load(tmp_path / "a" / "out.npy"), out.numpy()[rows.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "a" / "grad_weight.npy"), w.grad.numpy())

@@ -83,14 +83,14 @@ def test_graph_regression_training_loop():
 
 @pytest.mark.gpu
 def test_bench_default_run_ends_with_one_compact_strict_metric_line():
-    """Round-4 VERDICT item 1, on the real thing: `python bench.py` exactly as the driver runs it (C4, secondary configs, CPU baselines) - the
+    """Round-4 VERDICT item 1, on the real thing: `python bench.py --full` (C4, secondary configs, CPU baselines) - the
     LAST stdout line strict-parses, is < 4096 bytes and carries roofline.frac and cpu_baseline.value; the verbose record is on stderr."""
     import subprocess
     import sys
     from bench_util import parse_bench
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"], capture_output=True, text=True, timeout=900,
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--full"], capture_output=True, text=True, timeout=900,
                        env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d, det = parse_bench(r, need_cpu=True)
@@ -102,16 +102,48 @@ def test_bench_default_run_ends_with_one_compact_strict_metric_line():
 
 @pytest.mark.gpu
 def test_bench_c2l_line_is_compact_strict_and_names_the_fused_gr_kernel():
-    """`python bench.py --workload c2l` (the graph-regression leg): the same contract for its line - one strict-JSON line < 4096 bytes with
+    """`python bench.py --workload c2l --full` (the graph-regression leg): the same contract for its line - one strict-JSON line < 4096 bytes with
     `roofline` (K3 / K4 by their algorithmic bytes) and `cpu_baseline` (the GR oracle on a small batch); the per-call table is on stderr."""
     import subprocess
     import sys
     from bench_util import parse_bench
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, "bench.py", "--workload", "c2l", "--molecules", "2000", "--steps", "3", "--warmup", "1"], capture_output=True,
+    r = subprocess.run([sys.executable, "bench.py", "--workload", "c2l", "--molecules", "2000", "--steps", "3", "--warmup", "1", "--full"], capture_output=True,
                        text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d, det = parse_bench(r, need_cpu=True)
     assert d["scaling"] == "weak" and d["roofline"]["kernel"] in ("gr_fused_fwd", "gr_fused_bwd") and d["roofline_other"]["kernel"].startswith("gr_fused")
     assert {"gr_fused_fwd", "gr_fused_bwd", "gr_segsum", "tower_post_gw"} <= set(det["kernels"]) and det["kernels"]["gr_fused_fwd"]["bytes"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_its_dumped_outputs_repeat(tmp_path):
+    """A plain `python bench.py` times exactly --steps steps and does nothing the headline does not need (no CPU baseline, no plan-build
+    timing, no secondary configs); --dump-outputs writes what its last step computed, and two runs with the same arguments write the
+    same arrays."""
+    import subprocess
+    import sys
+    from bench_util import parse_bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ("run%d" % run)
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1", "--scale", "15", "--edges", "150000",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        d, det = parse_bench(r)
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+        assert abs(d["value"] - d["config"]["edges"] / d["ms_per_step"] * 1e3) <= 1e-3 * d["value"]
+        assert d["cpu_baseline"] is None and det["extra"] is None and det["plan_build"] is None
+        assert det["kernels"]["nc_fused_fwd"]["launches"] >= 4
+        dumps.append({f.name[:-4]: np.load(f) for f in sorted(out.glob("*.npy"))})
+    a, b = dumps
+    N = a["grad_x"].shape[0]
+    assert {"out", "grad_x", "sample_rows", "grad_weight", "grad_bias", "grad_mask_sum", "grad_mask_min"} <= set(a) and set(a) == set(b)
+    assert a["out"].shape == (N, 16) and a["grad_x"].shape == (N, 128) and a["grad_mask_max"].shape == (256, 128)
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        np.testing.assert_allclose(b[k], a[k], rtol=1e-5, atol=1e-6 * max(1.0, float(np.abs(a[k]).max())), err_msg=k)

@@ -54,12 +54,12 @@ def test_sharded_bench_line_explains_itself_two_ranks_one_device():
     """Round-3 VERDICT item 3: the N > 1 line of `bench.py` carries one record per rank (device identity, own / halo rows, edges, bytes
     sent and received per step, the rank's own ms per step, exchange time from events on a side stream in a separate instrumented pass, the compute stream's halo
     waits) in the DETAIL record (stderr), rank-max AND rank-mean step time, and the result of `--verify` (the sharded layer against the unsharded one on a 2^14-node
-    R-MAT, run before anything is timed - the default for N > 1).  Rehearsed here with gloo, both ranks on cuda:0."""
+    R-MAT, run before anything is timed - the default of --full at N > 1).  Rehearsed here with gloo, both ranks on cuda:0."""
     import json
     root = os.path.dirname(HERE)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--scale", "15", "--edges", "200000", "--steps", "3",
-                        "--warmup", "1", "--cpu-sample", "0", "--no-extra"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                        "--warmup", "1", "--cpu-sample", "0", "--no-extra", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     from bench_util import parse_bench
     d, det = parse_bench(r)
