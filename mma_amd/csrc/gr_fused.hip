@@ -779,7 +779,8 @@ __device__ __forceinline__ void blk_fwd_items(const GrParams& p, const DropParam
     const int b = L.rowptr[dn], deg = L.rowptr[dn + 1] - b;
     if (deg > kGroupMaxDeg) continue;                         // a long segment: left to the wave-per-node pass
     // ---- the item's loads, all issued before the first use: U row + three edge slots (slot i = edge min(i, deg-1); an
-    // empty segment re-reads the block's first edge and drops it)
+    // empty segment re-reads the block's first edge and drops it - the block has one: a block without edges never gets here, the
+    // kernel's p1 == p0 branch writes its zeros, so position p0 < p1 <= E is a staged word of this workgroup or an edge of the CSR)
     int j[3], e[3], pos[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {

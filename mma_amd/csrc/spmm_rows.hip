@@ -109,8 +109,11 @@ __global__ __launch_bounds__(kBlock) void segsum_block_kernel(const SegSumParams
     const int dn = (int)seg_udiv((uint32_t)it, p.qd_magic);
     const int c = (it - dn * (int)p.qd) * 4;
     const int b = s_rp[dn], deg = s_rp[dn + 1] - b;
+    // a long row is the tail's alone: other lanes write its sum into these LDS cells with no barrier in between, so a store of this
+    // item's zeros could land after it (it did: C = 32, the item in wavefront 1 behind seven 64-edge rows, the tail in wavefront 0)
+    if (deg > kSegLong) continue;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (deg <= kSegLong && deg > 0) {
+    if (deg > 0) {
       int j[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) j[i] = col_of(b + min(i, deg - 1));

@@ -551,8 +551,10 @@ class _LinearX3(torch.autograd.Function):
         OP = _round_up(fout, 128)
         fused = FUSED_PAD and x.is_cuda and x.dtype == torch.float32 and x.stride(1) == 1 and weight.dtype == torch.float32
         # [r5] the A operand is padded to 64 / 96 columns where [x | 1] fits (edge features 50 + 1, node features 75 + 1): the forward and
-        # the weight-gradient product stop reading, splitting and multiplying pad columns up to 128
-        KP = next(k for k in F16X2_K if fin + 1 <= k) if (X3_NARROW_K and USE_F16X2 and N >= _MIN_ROWS_X3) else 128
+        # the weight-gradient product stop reading, splitting and multiplying pad columns up to 128.  Only where gemm_bf16x3 hands the
+        # product to that kernel (its gate: OP <= 4096); the general kernel behind it takes K % 128 == 0 only
+        KP = (next(k for k in F16X2_K if fin + 1 <= k) if (X3_NARROW_K and USE_F16X2 and N >= _MIN_ROWS_X3 and OP <= 4096)
+              else 128)
         if row_index is not None and not fused:
             x = x.index_select(0, row_index.long())
         if fused:
