@@ -518,413 +518,6 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_kernel(cons
                                           kCgStoreAux);
 }
 
-// [r5] The two forward forms below (W-stationary, loader waves) are MEASUREMENT kernels: built, bit-equal to the column-group kernels,
-// and slower (C4 1.37 / 1.19-1.27 ms against 1.04).  They are compiled only with -DMMA_EXPERIMENTAL_FWD (make EXTRA=-DMMA_EXPERIMENTAL_FWD;
-// round-4 ADVICE: ~400 lines of slower kernels and an environment switch do not belong in the product library's hot path); without it
-// mma_gemm_f16x2_ws reports that, and MMA_FWD_WS is not read.
-#ifdef MMA_EXPERIMENTAL_FWD
-// ---- forward, W-STATIONARY (round 4): C (M, N) = x (M, K) W (K, N), K = 128 or 256, N % 256 == 0 ------------------------------------------
-// The column-group kernels above keep W in LDS and stream x through registers in the MFMA's fragment shape: 32 rows x 32 bytes per load
-// instruction - ~32 line requests to the texture addresser for 1 KB, and every 256-column (K = 256: 128-column) group of the same
-// rows loads them again.  Measurement builds at C4: the stores alone 0.75 ms, everything but the x loads 0.81, with them 1.04 - the
-// loads cost by being there, whether waited for or not (an asm-prefetched form changed nothing).  Here the roles are swapped:
-//   * a WAVE keeps its own 32 columns of W in registers for the whole launch (both fp16 pieces of all K/16 k-steps: 64 VGPRs at
-//     K = 128, 128 at K = 256) - there is no B slab in LDS, no fragment read of B, and LDS is free for x;
-//   * the eight waves of a workgroup (256 columns) load each 64-row (K = 256: 32-row) slice of x TOGETHER, row-major: one load
-//     instruction covers two whole rows (K = 256: one), 8 lines instead of 32; a row's maximum is a butterfly over the lanes that hold
-//     it, the power-of-two row scale and the split are done ONCE per row (not once per wave that multiplies it), and the fp16 pieces go to
-//     LDS in the MFMA's A-fragment order, [block][piece][k-step][lane][8 halves], which every wave then reads with lane-linear
-//     ds_read_b128 (conflict-free);
-//   * two LDS slots: iteration i multiplies slot i % 2 while the slice for iteration i+1 - requested at the top of iteration i, so that
-//     it is in flight behind the multiplications and is both issued and waited for inside ONE iteration (no load crosses the loop's
-//     back edge: hipcc merges entry and back edge into a full vmcnt drain otherwise) - is split and written to the other slot at the
-//     bottom; one barrier per iteration;
-//   * the stores of a finished 32 x 32 tile ride between the MFMAs of the next one (as in the column-group kernels, [r4]).
-// Same products in the same order as gemm_f16x2_colgroup_kernel (hi lo, lo hi into one accumulator, hi hi into the other, lo pieces
-// pre-scaled by 2^11): the results are bit-identical to it.  Bt2 = (2, N, K) as for mma_gemm_f16x2.
-template <int KS, int RBI>
-__global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_ws_kernel(const GemmParams p, const float* col_unscale, int64_t n_rgroups,
-                                                                     int n_cgroups, float* a_row_max) {
-  constexpr int K = 16 * KS;
-  constexpr int RI = 32 * RBI;                             // rows per iteration (a "row group")
-  constexpr int kKsP = 1024 + 32;                          // bytes per (piece, k-step) block of A fragments; the pad spreads the k-steps over the banks
-  constexpr int kPieceP = KS * kKsP, kBlkP = 2 * kPieceP;  // piece / 32-row block pitch
-  constexpr int kSlot = RBI * kBlkP + RI * 4;              // + the rows' scale exponents
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * kSlot];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r31 = lane & 31, h = lane >> 5;
-  const int xcd = blockIdx.x & 7, slot_id = blockIdx.x >> 3;
-  const int streams_per_xcd = kCgSlotsPerXcd / n_cgroups;
-  if (slot_id >= streams_per_xcd * n_cgroups) return;      // (before any barrier)
-  const int cg = slot_id % n_cgroups;
-  const int64_t stream = xcd * streams_per_xcd + slot_id / n_cgroups, n_streams = 8 * streams_per_xcd;
-  const int col0 = cg * 256 + wave * 32;                   // this wave's 32 columns
-
-  // W: this wave's columns, both pieces, every k-step - B[k][n]: lane (n = r31, h) holds k = 16 ks + 8 h + 0..7 of column col0 + r31
-  f16x8 wh[KS], wl[KS];
-  {
-    const _Float16* Bh = reinterpret_cast<const _Float16*>(p.Bt);
-    const _Float16* wp = Bh + (size_t)(col0 + r31) * K + 8 * h;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      wh[ks] = *reinterpret_cast<const f16x8*>(wp + ks * 16);
-      wl[ks] = *reinterpret_cast<const f16x8*>(wp + (size_t)p.N * K + ks * 16);
-    }
-  }
-  const int cue = (int)((__float_as_uint(col_unscale[col0 + r31]) >> 23) & 0xFF) - 127;     // log2 of this lane's column un-scale
-  const uint32_t c_off = (4u * h * (uint32_t)p.ldc + (uint32_t)r31) * 4u;
-  const uint32_t pcol = (uint32_t)col0 * 4u;
-
-  // producer role: this wave prepares rows [wave * 4 RBI, +4 RBI) of every row group; 4 float4 per lane, row-major
-  constexpr int C4 = K / 4;                                // float4 per row: 32 or 64
-  int p_row[4], p_k0[4];                                   // row inside the group and first k of the lane's float4 number i
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int f = lane + 64 * i;
-    p_row[i] = wave * (4 * RBI) + f / C4;
-    p_k0[i] = 4 * (f % C4);
-  }
-  float4 raw[4];
-#define MMA_WS_LOAD(G_)                                                                            \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                  \
-    const int64_t row = min((G_) * RI + p_row[i], p.M - 1);          /* rows past M re-read the last row; never stored */ \
-    raw[i] = *reinterpret_cast<const float4*>(p.A + row * p.lda + p_k0[i]);                        \
-  }
-// raw (rows of group G_) -> row maxima, scale exponents and fragment-ordered fp16 pieces in LDS slot S_
-#define MMA_WS_PRODUCE1(G_, S_, I_)                                                               \
-  {                                                                                                \
-    unsigned char* sl_ = lds + (S_) * kSlot;                                                       \
-    /* pins the part HERE: arithmetic on the loaded values is free to move up to the loads otherwise (IR-level code motion does not */ \
-    /* see sched_barrier) - and with it the wait for them, in front of the iteration's stores (seen in the K = 256 ISA: vmcnt(3)) */  \
-    asm volatile("" : "+v"(raw[I_].x), "+v"(raw[I_].y), "+v"(raw[I_].z), "+v"(raw[I_].w));          \
-    float rmax = fmaxf(0.f, fmaxf(fmaxf(fabsf(raw[I_].x), fabsf(raw[I_].y)), fmaxf(fabsf(raw[I_].z), fabsf(raw[I_].w))));   \
-    _Pragma("unroll") for (int o = 1; o < C4; o <<= 1) rmax = fmaxf(rmax, __shfl_xor(rmax, o, 64));            \
-    const int ex = (int)((__float_as_uint(rmax) >> 23) & 0xFF);                                    \
-    const int sce = min(max(14 - (ex - 127), -126), 127);            /* the row maximum lands in [2^14, 2^15) */ \
-    const float sc = __uint_as_float((uint32_t)(sce + 127) << 23);                                 \
-    if ((lane & (C4 - 1)) == 0) {                                    /* one lane per row */        \
-      reinterpret_cast<int*>(sl_ + RBI * kBlkP)[p_row[I_]] = sce;                                  \
-      const int64_t grow = (G_) * RI + p_row[I_];                                                  \
-      if (a_row_max && cg == 0 && grow < p.M) a_row_max[grow] = rmax;        /* for the weight-gradient product (TN form) */ \
-    }                                                                                              \
-    const float v[4] = {raw[I_].x * sc, raw[I_].y * sc, raw[I_].z * sc, raw[I_].w * sc};           \
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));                                       \
-    h4 hi, lo;                                                                                     \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                \
-      hi[j] = (_Float16)v[j];                                                                      \
-      lo[j] = (_Float16)((v[j] - (float)hi[j]) * 2048.f);                                          \
-    }                                                                                              \
-    const int blk_ = p_row[I_] >> 5, m_ = p_row[I_] & 31, k0 = p_k0[I_];                           \
-    unsigned char* d = sl_ + blk_ * kBlkP + (k0 >> 4) * kKsP + (m_ + 32 * ((k0 >> 3) & 1)) * 16 + (k0 & 7) * 2;  \
-    *reinterpret_cast<h4*>(d) = hi;                                                                \
-    *reinterpret_cast<h4*>(d + kPieceP) = lo;                                                      \
-  }
-#define MMA_WS_PRODUCE(G_, S_) { MMA_WS_PRODUCE1(G_, S_, 0) MMA_WS_PRODUCE1(G_, S_, 1) MMA_WS_PRODUCE1(G_, S_, 2) MMA_WS_PRODUCE1(G_, S_, 3) }
-
-  // the finished tile waiting to be stored: values, descriptor (ZERO bytes before the first tile: the range check drops those stores)
-  float prev[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) prev[r] = 0.f;
-  __amdgpu_buffer_rsrc_t crow_p = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, 0, 0x00020000);
-
-  if (stream < n_rgroups) {
-    MMA_WS_LOAD(stream)
-    MMA_WS_PRODUCE(stream, 0)
-  }
-  __syncthreads();
-  int it = 0;
-  for (int64_t gI = stream; gI < n_rgroups; gI += n_streams, ++it) {
-    const int64_t gN = gI + n_streams < n_rgroups ? gI + n_streams : gI;        // the last group requests its own rows again (4 loads, unused)
-    MMA_WS_LOAD(gN)
-    const unsigned char* sl = lds + (it & 1) * kSlot;
-#pragma unroll
-    for (int blk = 0; blk < RBI; ++blk) {
-      const int64_t row0 = gI * RI + blk * 32;
-      const int64_t rows_here = min((int64_t)32, p.M - row0);
-      const __amdgpu_buffer_rsrc_t crow = __builtin_amdgcn_make_buffer_rsrc(
-          p.C + min(row0, p.M - 1) * p.ldc, 0, rows_here > 0 ? (int)min((int64_t)0x7fffffff, rows_here * p.ldc * 4) : 0, 0x00020000);
-      f32x16 acc, acl;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acl[r] = 0.f; }
-      const unsigned char* fa = sl + blk * kBlkP + lane * 16;
-      f16x8 ah = *reinterpret_cast<const f16x8*>(fa), al = *reinterpret_cast<const f16x8*>(fa + kPieceP);
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        f16x8 nh = ah, nl = al;
-        if (ks + 1 < KS) {
-          nh = *reinterpret_cast<const f16x8*>(fa + (ks + 1) * kKsP);
-          nl = *reinterpret_cast<const f16x8*>(fa + kPieceP + (ks + 1) * kKsP);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        acl = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl[ks], acl, 0, 0, 0);
-        acl = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wh[ks], acl, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh[ks], acc, 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 16 / KS; ++j) {                          // 2 stores of the previous tile per k-step (K = 128), 1 (K = 256)
-          const int r = (16 / KS) * ks + j;
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(prev[r]), crow_p, c_off,
-                                                (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc) * 4u + pcol, kCgStoreAux);
-        }
-        // the NEXT group's rows, one load's worth (a row or two) every KS/4 k-steps of the group's last block: row maximum, scale, split
-        // and the LDS writes sit in the MFMAs' shadow like the stores do - at the bottom of the iteration all eight waves did them
-        // at once, with the matrix pipe and the store queue idle (1.36 ms at C4 against the column-group kernel's 1.10)
-        if (blk == RBI - 1 && (ks % (KS / 4)) == KS / 4 - 1) {
-          constexpr int dummy_ = 0; (void)dummy_;
-          switch (ks / (KS / 4)) {
-            case 0: MMA_WS_PRODUCE1(gN, (it + 1) & 1, 0) break;
-            case 1: MMA_WS_PRODUCE1(gN, (it + 1) & 1, 1) break;
-            case 2: MMA_WS_PRODUCE1(gN, (it + 1) & 1, 2) break;
-            default: MMA_WS_PRODUCE1(gN, (it + 1) & 1, 3) break;
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        ah = nh; al = nl;
-      }
-      // the scale exponents of the 16 rows this lane's accumulator registers hold, rows (r&3) + 8 (r>>2) + 4h - fetched now, not before
-      // the k-steps: at K = 256 (128 registers of W) sixteen more live registers through the loop meant spills
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int4 e4 = *reinterpret_cast<const int4*>(sl + RBI * kBlkP + (blk * 32 + 8 * q + 4 * h) * 4);
-        const int rse[4] = {e4.x, e4.y, e4.z, e4.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) prev[4 * q + j] = ldexpf(acc[4 * q + j] + acl[4 * q + j] * (1.f / 2048.f), cue - rse[j]);
-      }
-      crow_p = crow;
-    }
-    __syncthreads();
-  }
-#undef MMA_WS_LOAD
-#undef MMA_WS_PRODUCE
-#undef MMA_WS_PRODUCE1
-#pragma unroll
-  for (int r = 0; r < 16; ++r)
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(prev[r]), crow_p, c_off, (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc) * 4u + pcol,
-                                          kCgStoreAux);
-}
-
-// ---- forward, LOADER WAVES (round 4): the W-stationary kernel above with its two jobs given to different waves ---------------------------
-// What the W-stationary kernel taught: vmcnt is ONE in-order counter for loads and stores, so a wave that
-// stores tiles and also waits for rows of x waits for its own stores first.  Here waves 0-7 MULTIPLY (W in registers, A fragments from
-// LDS, tile stores between the MFMAs) and never issue a global load after their prologue - nothing they wait for stands behind a store;
-// waves 8-11 LOAD: each brings 16 of the row group's 64 rows in, row-major (whole lines), forms the row maxima, splits and writes the
-// fp16 pieces to the other LDS slot - their vmcnt queue holds loads only (plus one 4-byte row-maximum store per row).  One raw barrier per iteration (lgkmcnt only: a
-// __syncthreads() would also drain the multipliers' stores).  K = 128, N % 256 == 0; same products in the same order: the bits of
-// mma_gemm_f16x2.
-constexpr int kLwThreads = 768;          // 8 multiplier waves + 4 loader waves
-typedef float lw_f4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(kLwThreads, 1) void gemm_f16x2_lw_kernel(const GemmParams p, const float* col_unscale, int64_t n_rgroups,
-                                                                     int n_cgroups, float* a_row_max) {
-  constexpr int KS = 8, K = 128, RBI = 2, RI = 64;
-  constexpr int kKsP = 1024 + 32;
-  constexpr int kPieceP = KS * kKsP, kBlkP = 2 * kPieceP;
-  constexpr int kSlot = RBI * kBlkP + RI * 4;
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * kSlot];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r31 = lane & 31, h = lane >> 5;
-  const int xcd = blockIdx.x & 7, slot_id = blockIdx.x >> 3;
-  const int streams_per_xcd = kCgSlotsPerXcd / n_cgroups;
-  if (slot_id >= streams_per_xcd * n_cgroups) return;      // (before any barrier)
-  const int cg = slot_id % n_cgroups;
-  const int64_t stream = xcd * streams_per_xcd + slot_id / n_cgroups, n_streams = 8 * streams_per_xcd;
-  const int64_t n_it = stream < n_rgroups ? (n_rgroups - stream + n_streams - 1) / n_streams : 0;     // row groups of this workgroup
-#define MMA_LW_BARRIER() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
-
-  if (wave >= 8) {
-    // ---------------- loader: rows [32 lw, 32 lw + 32) of every row group; load i covers rows 2i, 2i+1 (lane >> 5), 16 bytes per lane
-    const int lw = wave - 8;                                  // 0..3: rows [16 lw, 16 lw + 16) of the group, load i = rows 2i, 2i+1
-    __builtin_amdgcn_s_setprio(3);                            // the loaders' short instruction stream goes ahead of the multipliers' MFMAs:
-                                                              // loaders + multipliers without stores 0.79 -> 0.71 ms, everything 1.27 -> 1.19
-    const int row_in = 16 * lw + h, k0 = 4 * r31;             // + 2 i
-    const uint32_t lda_b = (uint32_t)p.lda * 4u;
-    const uint32_t a_voff = (uint32_t)h * lda_b + (uint32_t)k0 * 4u, a_voff_c = (uint32_t)k0 * 4u;
-    lw_f4 rawA[8], rawB[8];
-// The loader's loads cross the loop's back edge (requested one iteration before they are split): hipcc then drains vmcnt at the loop head
-// (seen in the ISA: vmcnt(0) once per pair of iterations - the prefetch waited for on the spot), so they are inline asm with hand-placed
-// counted waits, as in gemm_f16x2_nlp_kernel: a wave-uniform SGPR base per row pair + one 32-bit lane offset, `s_nop 4` in front (the
-// base may come straight from a v_readlane: 5 wait states before a vector-memory instruction reads it), early-clobber outputs; the
-// wait names the registers it releases.  Rows past M: the base row is clamped to M-1 and the lane offset of the pair's second row to
-// the first (they are never stored).
-#define MMA_LW_LOAD(R_, IT_)                                                                       \
-    {                                                                                              \
-      const int64_t g_ = stream + min((int64_t)(IT_), n_it - 1) * n_streams;      /* past the end: the last group again (unused) */ \
-      _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                              \
-        const int64_t r_ = g_ * RI + 16 * lw + 2 * i;                                              \
-        const float* b_ = p.A + min(r_, p.M - 1) * p.lda;                                          \
-        const uint32_t vo_ = (r_ + 1 < p.M) ? a_voff : a_voff_c;                                   \
-        asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=&v"(R_[i]) : "v"(vo_), "s"(b_) : "memory");          \
-      }                                                                                            \
-    }
-// at most 8 younger operations in flight: releases the raw set R_ (and everything older)
-#define MMA_LW_WAIT8(R_)                                                                           \
-    asm volatile("s_waitcnt vmcnt(8)" : "+v"(R_[0]), "+v"(R_[1]), "+v"(R_[2]), "+v"(R_[3]), "+v"(R_[4]), "+v"(R_[5]), "+v"(R_[6]), "+v"(R_[7]) :: "memory");
-// three passes over the 8 row pairs, so that their dependency chains interleave: with the one-lane store of the row maximum inside the
-// per-pair loop every pair was its own basic block and the wave walked eight ~40-instruction chains one after the other
-#define MMA_LW_PRODUCE(R_, IT_, S_)                                                                \
-    {                                                                                              \
-      unsigned char* sl_ = lds + (S_) * kSlot;                                                     \
-      const int64_t g_ = stream + (int64_t)(IT_) * n_streams;                                      \
-      const bool real_ = (IT_) < n_it;                                                             \
-      float rmax_[8]; int sce_[8];                                                                 \
-      _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                              \
-        float rmax = fmaxf(0.f, fmaxf(fmaxf(fabsf(R_[i][0]), fabsf(R_[i][1])), fmaxf(fabsf(R_[i][2]), fabsf(R_[i][3]))));   \
-        /* maximum over the 32 lanes that hold the row: four DPP steps inside the 16-lane rows (quad xor 1, xor 2, half-row mirror, row */ \
-        /* mirror) and one swizzle across the two rows - as five ds_bpermute round trips per row the LOADERS set the kernel's pace */       \
-        rmax = fmaxf(rmax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(rmax), 0xB1, 0xF, 0xF, true)));   \
-        rmax = fmaxf(rmax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(rmax), 0x4E, 0xF, 0xF, true)));   \
-        rmax = fmaxf(rmax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(rmax), 0x141, 0xF, 0xF, true)));  \
-        rmax = fmaxf(rmax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(rmax), 0x140, 0xF, 0xF, true)));  \
-        rmax = fmaxf(rmax, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(rmax), 0x401F)));              \
-        const int ex = (int)((__float_as_uint(rmax) >> 23) & 0xFF);                                \
-        rmax_[i] = rmax;                                                                           \
-        sce_[i] = min(max(14 - (ex - 127), -126), 127);                                            \
-      }                                                                                            \
-      if (r31 == 0) {                                                /* one lane per row */        \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                            \
-          const int pr = row_in + 2 * i;                             /* row inside the group */    \
-          reinterpret_cast<int*>(sl_ + RBI * kBlkP)[pr] = sce_[i];                                 \
-          const int64_t grow = g_ * RI + pr;                                                       \
-          if (a_row_max && cg == 0 && real_ && grow < p.M) a_row_max[grow] = rmax_[i];             \
-        }                                                                                          \
-      }                                                                                            \
-      _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                              \
-        const float sc = __uint_as_float((uint32_t)(sce_[i] + 127) << 23);                         \
-        const float v[4] = {R_[i][0] * sc, R_[i][1] * sc, R_[i][2] * sc, R_[i][3] * sc};           \
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));                                   \
-        h4 hi, lo;                                                                                 \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                            \
-          hi[j] = (_Float16)v[j];                                                                  \
-          lo[j] = (_Float16)((v[j] - (float)hi[j]) * 2048.f);                                      \
-        }                                                                                          \
-        const int pr = row_in + 2 * i, m_ = pr & 31;                                               \
-        unsigned char* d = sl_ + (pr >> 5) * kBlkP + (k0 >> 4) * kKsP + (m_ + 32 * ((k0 >> 3) & 1)) * 16 + (k0 & 7) * 2;   \
-        *reinterpret_cast<h4*>(d) = hi;                                                            \
-        *reinterpret_cast<h4*>(d + kPieceP) = lo;                                                  \
-      }                                                                                            \
-    }
-    // two raw sets: the rows of group it+2 are requested before the rows of group it+1 are split (a full iteration ahead).  Four loader
-    // waves: with two, and the rows requested just before the barrier, the LOADERS set the pace (6.2 us per 64 rows against the ~3 us
-    // the multipliers' stores need: 1.59 ms at C4)
-    if (n_it > 0 && !(kAbl & 8)) {
-      MMA_LW_LOAD(rawA, 0)
-      MMA_LW_LOAD(rawB, 1)
-      MMA_LW_WAIT8(rawA)
-      MMA_LW_PRODUCE(rawA, 0, 0)
-    }
-    MMA_LW_BARRIER()
-    // whole pairs of iterations, then the odd one: no path on which a raw set is requested twice without a wait in between (the wait
-    // audit, tools/check_asm_waits.py, walks every path of the control-flow graph)
-    int64_t it = 0;
-    for (; it + 1 < n_it; it += 2) {
-      // multipliers are on group `it` (slot 0): group it+1 goes to slot 1, the rows of group it+2 are requested
-      if (!(kAbl & 8)) {
-        MMA_LW_LOAD(rawA, it + 2)
-        MMA_LW_WAIT8(rawB)
-        MMA_LW_PRODUCE(rawB, it + 1, 1)
-      }
-      MMA_LW_BARRIER()
-      if (!(kAbl & 8)) {
-        MMA_LW_LOAD(rawB, it + 3)
-        MMA_LW_WAIT8(rawA)
-        MMA_LW_PRODUCE(rawA, it + 2, 0)
-      }
-      MMA_LW_BARRIER()
-    }
-    if (it < n_it) MMA_LW_BARRIER()                         // the multipliers' last (odd) iteration: nothing left to bring in
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(rawA[0]), "+v"(rawA[1]), "+v"(rawA[2]), "+v"(rawA[3]), "+v"(rawA[4]), "+v"(rawA[5]), "+v"(rawA[6]), "+v"(rawA[7]),
-                 "+v"(rawB[0]), "+v"(rawB[1]), "+v"(rawB[2]), "+v"(rawB[3]), "+v"(rawB[4]), "+v"(rawB[5]), "+v"(rawB[6]), "+v"(rawB[7]) :: "memory");   // nothing in flight into dead registers at the end
-#undef MMA_LW_LOAD
-#undef MMA_LW_WAIT8
-#undef MMA_LW_PRODUCE
-    return;
-  }
-
-  // ---------------- multipliers
-  const int col0 = cg * 256 + wave * 32;
-  f16x8 wh[KS], wl[KS];
-  {
-    const _Float16* Bh = reinterpret_cast<const _Float16*>(p.Bt);
-    const _Float16* wp = Bh + (size_t)(col0 + r31) * K + 8 * h;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      wh[ks] = *reinterpret_cast<const f16x8*>(wp + ks * 16);
-      wl[ks] = *reinterpret_cast<const f16x8*>(wp + (size_t)p.N * K + ks * 16);
-    }
-  }
-  const int cue = (int)((__float_as_uint(col_unscale[col0 + r31]) >> 23) & 0xFF) - 127;
-  const uint32_t c_off = (4u * h * (uint32_t)p.ldc + (uint32_t)r31) * 4u;
-  const uint32_t pcol = (uint32_t)col0 * 4u;
-  float prev[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) prev[r] = 0.f;
-  __amdgpu_buffer_rsrc_t crow_p = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, 0, 0x00020000);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // W and the column un-scale have landed: no load is waited for below
-#define MMA_LW_CONSUME(IT_, S_)                                                                    \
-  {                                                                                                \
-    const unsigned char* sl = lds + (S_) * kSlot;                                                  \
-    const int64_t gI = stream + (int64_t)(IT_) * n_streams;                                        \
-    _Pragma("unroll") for (int blk = 0; blk < RBI; ++blk) {                                        \
-      const int64_t row0 = gI * RI + blk * 32;                                                     \
-      const int64_t rows_here = min((int64_t)32, p.M - row0);                                      \
-      const __amdgpu_buffer_rsrc_t crow = __builtin_amdgcn_make_buffer_rsrc(                       \
-          p.C + min(row0, p.M - 1) * p.ldc, 0, rows_here > 0 ? (int)min((int64_t)0x7fffffff, rows_here * p.ldc * 4) : 0, 0x00020000); \
-      f32x16 acc, acl;                                                                             \
-      _Pragma("unroll") for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acl[r] = 0.f; }               \
-      const unsigned char* fa = sl + blk * kBlkP + lane * 16;                                      \
-      f16x8 ah = *reinterpret_cast<const f16x8*>(fa), al = *reinterpret_cast<const f16x8*>(fa + kPieceP); \
-      _Pragma("unroll") for (int ks = 0; ks < KS; ++ks) {                                          \
-        f16x8 nh = ah, nl = al;                                                                    \
-        if (ks + 1 < KS) {                                                                         \
-          nh = *reinterpret_cast<const f16x8*>(fa + (ks + 1) * kKsP);                              \
-          nl = *reinterpret_cast<const f16x8*>(fa + kPieceP + (ks + 1) * kKsP);                    \
-        }                                                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-        if (!(kAbl & 2)) {                                                                         \
-        acl = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl[ks], acl, 0, 0, 0);                    \
-        acl = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wh[ks], acl, 0, 0, 0);                    \
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh[ks], acc, 0, 0, 0);                    \
-        } else { asm volatile("" :: "v"(ah), "v"(al), "v"(wh[ks]), "v"(wl[ks])); }                 \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                            \
-          const int r = 2 * ks + j;                                                                \
-          if (!(kAbl & 4)) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(prev[r]), crow_p, c_off, \
-                                                (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc) * 4u + pcol, kCgStoreAux); \
-          else asm volatile("" :: "v"(prev[r]));                                                   \
-        }                                                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-        ah = nh; al = nl;                                                                          \
-      }                                                                                            \
-      _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                              \
-        const int4 e4 = *reinterpret_cast<const int4*>(sl + RBI * kBlkP + (blk * 32 + 8 * q + 4 * h) * 4); \
-        const int rse[4] = {e4.x, e4.y, e4.z, e4.w};                                               \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j)                                              \
-          prev[4 * q + j] = ldexpf(acc[4 * q + j] + acl[4 * q + j] * (1.f / 2048.f), cue - rse[j]); \
-      }                                                                                            \
-      crow_p = crow;                                                                               \
-    }                                                                                              \
-  }
-  MMA_LW_BARRIER()                                                                                 // slot 0 holds the first group
-  int64_t it = 0;
-  for (; it + 1 < n_it; it += 2) {
-    MMA_LW_CONSUME(it, 0)
-    MMA_LW_BARRIER()
-    MMA_LW_CONSUME(it + 1, 1)
-    MMA_LW_BARRIER()
-  }
-  if (it < n_it) {
-    MMA_LW_CONSUME(it, 0)
-    MMA_LW_BARRIER()
-  }
-#undef MMA_LW_CONSUME
-#undef MMA_LW_BARRIER
-#pragma unroll
-  for (int r = 0; r < 16; ++r)
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(prev[r]), crow_p, c_off, (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc) * 4u + pcol,
-                                          kCgStoreAux);
-}
-
-#endif  // MMA_EXPERIMENTAL_FWD
-
 // ---- K == 256, three products (round 2, late): the forward [P|Q] = x [Wtop|Wbot] of hidden width 256 (C5) -----------------------------
 // The column-group form with a 256-deep reduction: a workgroup owns 128 columns, their B slab (2 pieces x 128 columns x 256 k fp16 = 135 KB
 // with the row padding) stays in LDS for the whole launch, a wave's 32 rows (256 floats each) are loaded once, scaled by the power of
@@ -1335,18 +928,16 @@ __global__ __launch_bounds__(kNlThreads, 1) void gemm_x3_n128_kernel(const GemmP
 }
 
 // ---- N == 128, long K, three products (round 2): gemm_x3_n128_kernel with fp16 x 2 pieces -------------------------------------
-// Same structure (8 waves = 256 rows, whole-chunk slab, one barrier per K chunk, pipelined fragments, atomic C +=), half the
+// Same structure (8 waves = 256 rows, whole-chunk slab, one barrier per K chunk, pipelined fragments), half the
 // MFMAs.  The row scale comes from row_max (>= the row's maximum |a|, produced by the kernels that wrote A); both un-scalings
-// are one ldexp in the epilogue.  Handles a ragged M itself (rows past M re-read the last row, their stores / atomics are
+// are one ldexp in the epilogue.  Handles a ragged M itself (rows past M re-read the last row, their stores are
 // dropped by the buffer range check).
 constexpr int kHnSlab = 2 * kNlPiece;                    // 36 864 B per K chunk (two fp16 pieces of all 128 columns)
 
-// ACC: 0 = C = A B, 1 = C += A B by one float atomic per element, 2 = C += A B by a plain read - add - store of the tile (every element has
-// exactly one writer either way, so both accumulate forms give the same bits: old + product, one rounding).  Round 4: the atomic form
-// issues 64 atomics per wave at the end of every 256-row unit, all eight waves of the one workgroup a CU holds at once, and float
-// atomics execute at the memory side at ~1.3 TB/s chip-wide, one 256-byte wave-instruction per ~50 ns per CU
-// (MI355X_MICROARCH.md "Global float atomics"): 512 of them are ~25 us of a 75 us unit with nothing else running on the CU.  Form 2
-// fetches the 64 old values in one batch when the last chunk's MFMAs are done (the A / slab prefetch registers are dead by then).
+// ACC: 0 = C = A B, 2 = C += A B by a plain read - add - store of the tile (every element has exactly one writer: old + product, one
+// rounding).  The 64 old values are fetched in one batch when the last chunk's MFMAs are done (the A / slab prefetch registers are dead
+// by then).  (Value 1 was round 3's epilogue of one float atomic per element, ~25 us of a 75 us unit - DESIGN.md; the values keep
+// their numbers so that the kernels keep their symbol names.)
 template <int ACC>
 __global__ __launch_bounds__(kNlThreads, 1) void gemm_f16x2_n128_kernel(const GemmParams p, const float* row_max, const float* col_unscale,
                                                                         int64_t n_units) {
@@ -1474,8 +1065,7 @@ __global__ __launch_bounds__(kNlThreads, 1) void gemm_f16x2_n128_kernel(const Ge
         const int rse = __shfl(sce, (r & 3) + 8 * (r >> 2) + 4 * h, 64);          // once per 256 x 128 block: not worth 16 registers
         const float val = ldexpf(acc[t][r] + acl[t][r] * (1.f / 2048.f), cue - rse);
         const uint32_t so = (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc + t * 32) * 4u;
-        if (ACC == 1) __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(val, crow, c_off, so, 0);
-        else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), crow, c_off, so, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), crow, c_off, so, 0);
       }
     }
   }
@@ -1750,8 +1340,7 @@ __global__ __launch_bounds__(kNlThreads, 1) void gemm_f16x2_nlp_kernel(const Gem
           const int rse = __shfl(sce, (r & 3) + 8 * (r >> 2) + 4 * h, 64);
           const float val = ldexpf(acc[t0 + t][r], cue - rse);
           const uint32_t so = (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc + (t0 + t) * 32) * 4u;
-          if (ACC == 1) __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(val, crow, c_off, so, 0);
-          else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ACC == 2 ? oldv[t][r] + val : val), crow, c_off, so, 0);
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ACC == 2 ? oldv[t][r] + val : val), crow, c_off, so, 0);
         }
       }
     }
@@ -2436,23 +2025,6 @@ extern "C" int mma_gemm_f16x2(const float* A, int64_t lda, const void* Bt2, cons
   MMA_REQUIRE(A && Bt2 && col_unscale && C && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(Bt2) & 15) == 0,
               "NULL or misaligned argument");
   GemmParams p{A, lda, static_cast<const __bf16*>(Bt2), C, ldc, M, N, 128, 0};
-#ifdef MMA_EXPERIMENTAL_FWD
-  // MMA_FWD_WS=1: the W-stationary kernel (A/B switch, read per call).  Measured SLOWER than the column-group kernel (C4 1.37 vs 1.06 ms,
-  // C5 8.4 vs 7.8 ms): its waves meet at a barrier every 64 rows, and a wave's wait for the next rows is a wait for every store it issued
-  // before them (one in-order vmcnt) - see DESIGN.md "forward GEMM, round 4"; kept for the next step (loader waves that never store).
-  const char* ws_env = getenv("MMA_FWD_WS");
-  const bool use_ws = ws_env && ws_env[0] == '1';
-  if (ws_env && ws_env[0] == '2' && N % 256 == 0 && (kCgSlotsPerXcd % (N / 256)) == 0) {         // MMA_FWD_WS=2: loader waves
-    hipLaunchKernelGGL(gemm_f16x2_lw_kernel, dim3(256), dim3(kLwThreads), 0, static_cast<hipStream_t>(stream), p, col_unscale, (M + 63) / 64,
-                       N / 256, a_row_max);
-    return check_launch("gemm_f16x2_lw_kernel");
-  }
-  if (use_ws && N % 256 == 0 && (kCgSlotsPerXcd % (N / 256)) == 0) {
-    hipLaunchKernelGGL((gemm_f16x2_ws_kernel<8, 2>), dim3(256), dim3(kCgThreads), 0, static_cast<hipStream_t>(stream), p, col_unscale,
-                       (M + 63) / 64, N / 256, a_row_max);
-    return check_launch("gemm_f16x2_ws_kernel");
-  }
-#endif
   const int64_t n_units = (M + kCgRows - 1) / kCgRows;
   const int groups = N / 128;
   if (groups % 2 == 0)        // pairs of column groups per workgroup
@@ -2527,27 +2099,6 @@ extern "C" int mma_gemm_f16x2_k256p(const void* Ap, const int32_t* sce, const vo
   return check_launch("gemm_f16x2_colgroup_k256p_kernel");
 }
 
-extern "C" int mma_gemm_f16x2_ws(const float* A, int64_t lda, const void* Bt2, const float* col_unscale, float* C, int64_t ldc,
-                                 float* a_row_max, int64_t M, int32_t N, int32_t K, void* stream) {
-  MMA_REQUIRE(M >= 0 && (K == 128 || K == 256) && N >= 256 && N % 256 == 0 && (kCgSlotsPerXcd % (N / 256)) == 0,
-              "M=%lld N=%d K=%d: need K in {128, 256}, N %% 256 == 0 and N / 256 dividing %d", (long long)M, N, K, kCgSlotsPerXcd);
-  MMA_REQUIRE(lda >= K && ldc >= N && lda % 4 == 0 && lda < (1 << 24) && ldc < (1 << 24), "row pitch too small, unaligned or >= 2^24");
-  if (M == 0) return 0;
-  MMA_REQUIRE(A && Bt2 && col_unscale && C && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(Bt2) & 15) == 0,
-              "NULL or misaligned argument");
-#ifdef MMA_EXPERIMENTAL_FWD
-  GemmParams p{A, lda, static_cast<const __bf16*>(Bt2), C, ldc, M, N, K, 0};
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (K == 128) hipLaunchKernelGGL((gemm_f16x2_ws_kernel<8, 2>), dim3(256), dim3(kCgThreads), 0, st, p, col_unscale, (M + 63) / 64, N / 256, a_row_max);
-  else hipLaunchKernelGGL((gemm_f16x2_ws_kernel<16, 1>), dim3(256), dim3(kCgThreads), 0, st, p, col_unscale, (M + 31) / 32, N / 256, a_row_max);
-  return check_launch("gemm_f16x2_ws_kernel");
-#else
-  (void)a_row_max; (void)stream;
-  return fail(3, "mma_gemm_f16x2_ws: built without -DMMA_EXPERIMENTAL_FWD (the W-stationary / loader-wave forward kernels are measurement "
-                 "forms, slower than mma_gemm_f16x2 / _k256; `make -C mma_amd/csrc clean all EXTRA=-DMMA_EXPERIMENTAL_FWD` builds them)");
-#endif
-}
-
 extern "C" int mma_gemm_f16x2_n128(const float* A, int64_t lda, const float* row_max, const void* Bt2, const float* col_unscale, float* C,
                                    int64_t ldc, int64_t M, int32_t K, int32_t accumulate, void* stream) {
   MMA_REQUIRE(M >= 0 && K >= kNlKC && K % kNlKC == 0 && K <= (1 << 20), "M=%lld K=%d: need K %% 64 == 0", (long long)M, K);
@@ -2559,9 +2110,7 @@ extern "C" int mma_gemm_f16x2_n128(const float* A, int64_t lda, const float* row
   const int64_t n_units = (M + kNlRows - 1) / kNlRows;
   const dim3 g((unsigned)(n_units < 256 ? n_units : 256));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  static const bool acc_atomic = getenv("MMA_DX_ACC") && getenv("MMA_DX_ACC")[0] == 'a';     // MMA_DX_ACC=atomic: round 3's epilogue (A/B switch)
-  if (accumulate && acc_atomic) hipLaunchKernelGGL(gemm_f16x2_n128_kernel<1>, g, dim3(kNlThreads), 0, st, p, row_max, col_unscale, n_units);
-  else if (accumulate) hipLaunchKernelGGL(gemm_f16x2_n128_kernel<2>, g, dim3(kNlThreads), 0, st, p, row_max, col_unscale, n_units);
+  if (accumulate) hipLaunchKernelGGL(gemm_f16x2_n128_kernel<2>, g, dim3(kNlThreads), 0, st, p, row_max, col_unscale, n_units);
   else hipLaunchKernelGGL(gemm_f16x2_n128_kernel<0>, g, dim3(kNlThreads), 0, st, p, row_max, col_unscale, n_units);
   return check_launch("gemm_f16x2_n128_kernel");
 }
@@ -2578,12 +2127,9 @@ extern "C" int mma_gemm_f16x2_nlp(const float* A, int64_t lda, const float* row_
   const int64_t n_units = (M + kNlRows - 1) / kNlRows;
   const dim3 g((unsigned)(n_units < 256 ? n_units : 256));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  static const bool acc_atomic = getenv("MMA_DX_ACC") && getenv("MMA_DX_ACC")[0] == 'a';
-  const int mode = accumulate ? (acc_atomic ? 1 : 2) : 0;
-#define MMA_NLP_LAUNCH(NT_)                                                                                                        \
-  if (mode == 0) hipLaunchKernelGGL((gemm_f16x2_nlp_kernel<NT_, 0>), g, dim3(kNlThreads), 0, st, p, row_max, col_unscale, n_units);      \
-  else if (mode == 1) hipLaunchKernelGGL((gemm_f16x2_nlp_kernel<NT_, 1>), g, dim3(kNlThreads), 0, st, p, row_max, col_unscale, n_units); \
-  else hipLaunchKernelGGL((gemm_f16x2_nlp_kernel<NT_, 2>), g, dim3(kNlThreads), 0, st, p, row_max, col_unscale, n_units);
+#define MMA_NLP_LAUNCH(NT_)                                                                                                     \
+  if (accumulate) hipLaunchKernelGGL((gemm_f16x2_nlp_kernel<NT_, 2>), g, dim3(kNlThreads), 0, st, p, row_max, col_unscale, n_units); \
+  else hipLaunchKernelGGL((gemm_f16x2_nlp_kernel<NT_, 0>), g, dim3(kNlThreads), 0, st, p, row_max, col_unscale, n_units);
   if (N == 128) { MMA_NLP_LAUNCH(4) } else { MMA_NLP_LAUNCH(8) }
 #undef MMA_NLP_LAUNCH
   return check_launch("gemm_f16x2_nlp_kernel");

@@ -8,6 +8,7 @@ batch) fills the chip: 140 TFLOP/s, 89 % of the fp32 MFMA peak (0.97 ms instead 
 import torch
 
 from . import _lib
+from ._env import flag, integer
 from ._lib import call, ptr, stream_ptr
 
 
@@ -18,9 +19,9 @@ def _span(name, nbytes=0, flops=0, mfma=None):
 _ROWS_PER_BATCH = 8192
 USE_BF16X3 = True     # fp32-accurate GEMM on the bf16 matrix cores (csrc/gemm_x3.hip) where the shape allows
 _MIN_ROWS_X3 = 4096
-_MIN_COLS_TN = int(__import__("os").environ.get("MMA_MIN_COLS_TN", "1"))
-_MIN_ROWS_TN = int(__import__("os").environ.get("MMA_MIN_ROWS_TN", "1024"))    # the TN kernel from here on (Cora's 2 708 rows: the library's
-                                                                              # 128 x 256 x 2708 TN product takes 22-25 us, a fifth of the layer replay)
+_MIN_COLS_TN = integer("MMA_MIN_COLS_TN", 1)
+_MIN_ROWS_TN = integer("MMA_MIN_ROWS_TN", 1024)    # the TN kernel from here on (Cora's 2 708 rows: the library's 128 x 256 x 2708 TN
+                                                   # product takes 22-25 us, a fifth of the layer replay)
 
 
 def _x3_ok(a, w):
@@ -61,19 +62,11 @@ def _split_f16x2(w, plain_lo=False):
     return bt2, cu
 
 
-PACK_K256 = __import__("os").environ.get("MMA_PACK_K256", "1") != "0"        # 0: round 4's K = 256 forward (fp32 rows split per column group)
-USE_F16X2_N128 = __import__("os").environ.get("MMA_F16X2_DX", "1") != "0"
-USE_F16X2_K256 = __import__("os").environ.get("MMA_F16X2_K256", "1") != "0"
-
-
-def ws_ok(N):
-    """mma_gemm_f16x2_ws takes N: whole 256-column groups, a divisor of the 32 workgroup slots of an XCD.  Opt-in (MMA_FWD_WS=1) AND only in
-    a library built with -DMMA_EXPERIMENTAL_FWD [r5]: measured slower than the column-group kernels (gemm_x3.hip)."""
-    return N % 256 == 0 and 32 % (N // 256) == 0 and __import__("os").environ.get("MMA_FWD_WS", "0") == "1"
+PACK_K256 = flag("MMA_PACK_K256")        # 0: round 4's K = 256 forward (fp32 rows split per column group)
 
 
 def f16x2_n128_ok(M, K, N):
-    return (USE_F16X2 and USE_F16X2_N128 and USE_BF16X3 and N % 128 == 0 and N <= 512 and K % 64 == 0 and K > 128 and M >= (1 << 16))
+    return (USE_F16X2 and USE_BF16X3 and N % 128 == 0 and N <= 512 and K % 64 == 0 and K > 128 and M >= (1 << 16))
 
 
 def row_absmax(a):
@@ -86,7 +79,7 @@ def row_absmax(a):
     return out
 
 
-USE_NLP = __import__("os").environ.get("MMA_DX_NLP", "1") != "0"      # round 4: the pipelined one-accumulator form (0: round 3's kernel)
+USE_NLP = flag("MMA_DX_NLP")      # round 4: the pipelined one-accumulator form (0: round 3's kernel)
 
 
 def gemm_f16x2_n128(a, row_max, w, out, accumulate=False):
@@ -136,23 +129,13 @@ def gemm_bf16x3(a, w, out=None, accumulate=False, row_max_box=None):
         if rm is not None:
             row_max_box.append(rm)
         return gemm_f16x2(a, w, out, rm)
-    if (USE_F16X2 and USE_F16X2_N128 and not accumulate and K > 128 and N > 128 and K % 64 == 0 and N % 128 == 0 and M >= (1 << 16)
+    if (USE_F16X2 and not accumulate and K > 128 and N > 128 and K % 64 == 0 and N % 128 == 0 and M >= (1 << 16)
             and (out is None or (out.stride(1) == 1 and out.dtype == torch.float32))):
         # hidden width 256 (C5): K = 256 does not fit the whole-row form of mma_gemm_f16x2; the chunked three-product kernel
         # takes the row maxima from one cheap pass over `a` (M x K floats read against M x N written)
         if out is None:
             out = torch.empty((M, N), device=a.device, dtype=torch.float32)
-        if K == 256 and ws_ok(N):
-            # W-stationary kernel (round 4): forms the row maxima itself (and leaves them for the weight-gradient product) - no separate
-            # pass over `a`
-            rm = torch.empty((M,), device=a.device, dtype=torch.float32)
-            if row_max_box is not None:
-                row_max_box.append(rm)
-            bt2, cu = _split_f16x2(w)
-            with _span("gemm_x3_persist", nbytes=4 * M * (K + N), flops=2 * M * K * N, mfma="f16x3"):
-                call("mma_gemm_f16x2_ws", ptr(a), a.stride(0), ptr(bt2), ptr(cu), ptr(out), out.stride(0), ptr(rm), M, N, K, stream_ptr())
-            return out
-        if K == 256 and N <= 4096 and USE_F16X2_K256 and PACK_K256:
+        if K == 256 and N <= 4096 and PACK_K256:
             # [r5] A packed once into fp16 fragment order (one pass: row maxima, scale exponents, both pieces) - the 32 column groups of
             # hidden width 256 stop re-loading the rows in the MFMA's fragment shape and re-splitting them (C5 shard: 7.7 -> see DESIGN.md)
             rm = torch.empty((M,), device=a.device, dtype=torch.float32)
@@ -169,7 +152,7 @@ def gemm_bf16x3(a, w, out=None, accumulate=False, row_max_box=None):
         rm = row_absmax(a)
         if row_max_box is not None:
             row_max_box.append(rm)
-        if K == 256 and N <= 4096 and USE_F16X2_K256:
+        if K == 256 and N <= 4096:
             # column-group form with the whole 256-deep B slab resident: A is read once per column group through L2 instead of once per
             # 128-column launch from HBM (C5 forward, N = 4096: 32 launches of the chunked kernel)
             bt2, cu = _split_f16x2(w)
@@ -292,11 +275,8 @@ def gemm_bf16x3_tn(x, g):
     return out
 
 
-USE_F16X2_TN = __import__("os").environ.get("MMA_F16X2_TN", "1") != "0"
 _MIN_ROWS_F16X2_TN = 1 << 16
-
-
-TN_KA256 = __import__("os").environ.get("MMA_TN_KA256", "1") != "0"       # 0: 128-column blocks of x, one launch each (round 3)
+TN_KA256 = flag("MMA_TN_KA256")       # 0: 128-column blocks of x, one launch each (round 3)
 
 
 def gemm_f16x2_tn(x, g, x_row_max=None, g_row_max=None):
@@ -322,7 +302,7 @@ def xt_g(x, g, x_row_max=None, g_row_max=None):
     """x^T @ g for tall x (N,in), g (N,out): the TN kernels where the shape allows (three products when the caller brings g's row
     maxima along - a pass over the wide operand would cost what the form saves -, else six), else split-N batched GEMM + sum."""
     if _x3_tn_ok(x, g):
-        if USE_F16X2 and USE_F16X2_TN and g_row_max is not None and x.shape[0] >= _MIN_ROWS_F16X2_TN:
+        if USE_F16X2 and g_row_max is not None and x.shape[0] >= _MIN_ROWS_F16X2_TN:
             return gemm_f16x2_tn(x, g, x_row_max, g_row_max)
         return gemm_bf16x3_tn(x, g)
     N = x.shape[0]
@@ -379,7 +359,6 @@ def col_sum(g):
     return out
 
 
-USE_SKINNY = __import__("os").environ.get("MMA_SKINNY_LINEAR", "1") != "0"
 _SKINNY_MIN_ROWS = 4096
 
 
@@ -387,7 +366,7 @@ def _skinny_ok(x2, weight):
     """K16: tall fp32 rows through a narrow Linear (out <= 80, in <= 512): the 75 -> 75 layers of graph regression.  rocBLAS runs
     them at ~0.11 ms per GEMM on 2e5 rows (61 MB in, 61 MB out); the fp32 matrix-core kernels stream them."""
     O, K = weight.shape
-    return (USE_SKINNY and x2.is_cuda and x2.dtype == torch.float32 and weight.dtype == torch.float32 and x2.dim() == 2
+    return (x2.is_cuda and x2.dtype == torch.float32 and weight.dtype == torch.float32 and x2.dim() == 2
             and x2.shape[0] >= _SKINNY_MIN_ROWS and O <= 80 and K <= 512 and x2.stride(1) == 1
             and tower_post_fits(K, -(-O // 16)))     # the kernels' own limits (weights + wave tiles inside 160 KB of LDS, both layouts)
 
@@ -410,7 +389,7 @@ def _skinny_weights(weight):
     return Wa, Wb
 
 
-SKINNY_GW = __import__("os").environ.get("MMA_SKINNY_GW", "1") != "0"      # 0: round 4's TN GEMM + column sum (A/B)
+SKINNY_GW = flag("MMA_SKINNY_GW")      # 0: round 4's TN GEMM + column sum (A/B)
 
 
 def skinny_gw(g2, x2, want_bias=True):
@@ -447,7 +426,7 @@ class _Linear(torch.autograd.Function):
             if addend is not None:
                 add2 = addend.reshape(-1, O)
                 add2 = add2 if add2.stride(1) == 1 else add2.contiguous()
-            x3 = add2 is None and __import__("os").environ.get("MMA_SKINNY_X3", "1") != "0" and __import__("os").environ.get("MMA_POST_EXACT") != "1"
+            x3 = add2 is None and flag("MMA_SKINNY_X3") and not flag("MMA_POST_EXACT", default=False)
             with _span("skinny_linear_fwd", nbytes=4 * x2.shape[0] * (K + O * (2 if add2 is not None else 1)), flops=2 * x2.shape[0] * Wa.shape[0] * Wa.shape[1],
                        mfma="bf16x6" if x3 else "f32"):
                 call("mma_skinny_linear_fwd", ptr(x2), x2.stride(0), ptr(Wa), ptr(bias.contiguous() if bias is not None else None), ptr(add2),
@@ -503,10 +482,8 @@ def linear(x, weight, bias=None, addend=None):
 # K = 128 and N % 128 == 0 they are ordinary inputs of the bf16x3 kernels.  The ones column that carries the bias sits in the
 # K padding, so forward folds the bias in and the TN weight-gradient GEMM returns the bias gradient as one more row.
 X3_LINEAR = True
-FUSED_PAD = __import__("os").environ.get("MMA_PAD_ONES", "1") != "0"        # 0: torch's pad + a strided fill (round 3)
+FUSED_PAD = flag("MMA_PAD_ONES")        # 0: torch's pad + a strided fill (round 3)
 X3_LINEAR_MIN_ROWS = 32768
-X3_ROW_MAX = __import__("os").environ.get("MMA_X3_ROW_MAX", "1") != "0"     # 0: round 4's six-product backward of the tall Linears (A/B)
-X3_NARROW_K = __import__("os").environ.get("MMA_X3_NARROW_K", "1") != "0"   # 0: every padded A operand 128 columns wide (A/B)
 _PADDED = {}          # data_ptr -> weakref to a (rows, pitch) fp32 buffer whose columns beyond the payload are ZERO
 
 
@@ -553,7 +530,7 @@ class _LinearX3(torch.autograd.Function):
         # [r5] the A operand is padded to 64 / 96 columns where [x | 1] fits (edge features 50 + 1, node features 75 + 1): the forward and
         # the weight-gradient product stop reading, splitting and multiplying pad columns up to 128.  Only where gemm_bf16x3 hands the
         # product to that kernel (its gate: OP <= 4096); the general kernel behind it takes K % 128 == 0 only
-        KP = (next(k for k in F16X2_K if fin + 1 <= k) if (X3_NARROW_K and USE_F16X2 and N >= _MIN_ROWS_X3 and OP <= 4096)
+        KP = (next(k for k in F16X2_K if fin + 1 <= k) if (USE_F16X2 and N >= _MIN_ROWS_X3 and OP <= 4096)
               else 128)
         if row_index is not None and not fused:
             x = x.index_select(0, row_index.long())
@@ -598,7 +575,7 @@ class _LinearX3(torch.autograd.Function):
         gx = gw = gb = None
         # [r5] the producer of g (K4 + the dV segment sum) left max |g row| with its padded buffer: both products take the THREE-product
         # fp16 x 2 kernels (round 4: six bf16 products, because nobody knew the row maxima - 15 % of the C2L step)
-        g_rm = getattr(gp, "_mma_row_max", None) if (USE_F16X2 and USE_F16X2_TN and X3_ROW_MAX) else None
+        g_rm = getattr(gp, "_mma_row_max", None) if USE_F16X2 else None
         three = g_rm is not None and xp.shape[0] >= _MIN_ROWS_F16X2_TN
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
             KA = _round_up(fin + 1, 32)

@@ -1,11 +1,11 @@
 """autograd wrappers over the C ABI (include/mma_amd.h).  Tensors are plumbing: every FLOP and byte of the
 hot path moves inside libmma_amd.so; torch only owns the memory, the stream and the autograd tape."""
 
-import os
 
 import torch
 
 from . import _lib
+from ._env import flag
 from ._lib import call, host_codes, ptr, require_gpu, stream_ptr
 
 # K2b form for the reduce_k (shared upstream gradient) backward.  True: dL/ds_k is rebuilt per edge from ONE packed row per
@@ -16,7 +16,7 @@ SHARED_GRAD_BWD = True
 # Round 3: with the shared-gradient form K1 leaves the packed code rows itself (no aux rows written by K2a), and the node-level
 # backward (K2a: gP = g dm/ds T, the direct term of dL/dx) runs in K2b's per-source epilogue - no K2a launch, no gxs round trip.
 # False: K2a stays a launch of its own (reading the code rows).  Both forms are covered by the parity tests.
-FUSE_NODE_BWD = os.environ.get("MMA_FUSE_NODE_BWD", "1") != "0"
+FUSE_NODE_BWD = flag("MMA_FUSE_NODE_BWD")
 TIMER = None   # bench.py installs an object with .span(name) -> context manager (HIP events around the calls)
 
 
@@ -586,7 +586,7 @@ class _GRAggregate(torch.autograd.Function):
         # [r5] with their row maxima (K4 and the dV segment sum merge max |row| into one zeroed (E + N,) array): the GEMMs behind take three
         # products instead of six
         pad_m, pad_u = tall and has_z and E >= dense.X3_LINEAR_MIN_ROWS, tall and fused and N >= dense.X3_LINEAR_MIN_ROWS
-        rm = torch.zeros((E + N,), device=gout.device, dtype=torch.float32) if (pad_m or pad_u) and dense.X3_ROW_MAX and E > 0 else None
+        rm = torch.zeros((E + N,), device=gout.device, dtype=torch.float32) if (pad_m or pad_u) and E > 0 else None
         gmsg = (dense.padded_empty(E, D, gout.device, row_max=rm[:E] if rm is not None else None) if pad_m
                 else torch.empty((E, D), device=gout.device, dtype=torch.float32))
         if E == 0:
@@ -654,7 +654,7 @@ class _TowerPost(torch.autograd.Function):
         pre = cache[1] if cache is not None and cache[0] == key else None
         # agg rows in, y rows out, the scaler table; S x 16 padded outputs per (node, tower, kf) on the fp32 matrix cores
         # (K13 runs on three bf16 pieces per operand, six piece products, where its split weights fit the LDS and MMA_POST_EXACT is unset)
-        x3 = os.environ.get("MMA_POST_EXACT") != "1" and (KFp // 32) * S * 3 * 1024 <= 160 * 1024
+        x3 = not flag("MMA_POST_EXACT", default=False) and (KFp // 32) * S * 3 * 1024 <= 160 * 1024
         with _span("tower_post_fwd", nbytes=4 * N * (T * KF + T * O + 8), flops=2 * N * T * KFp * S * 16, mfma="bf16x6" if x3 else "f32"):
             if pre is None:
                 pre = torch.empty((N, 8), device=agg.device, dtype=torch.float32)

@@ -6,7 +6,9 @@ graph on the host with numpy and then lives in HBM as int32."""
 import numpy as np
 import torch
 
-DEVICE_PLAN = __import__("os").environ.get("MMA_DEVICE_PLAN", "1") != "0"     # 0: the host numpy builders (round 2)
+from ._env import flag, integer
+
+DEVICE_PLAN = flag("MMA_DEVICE_PLAN")     # 0: the host numpy builders (round 2)
 DEFAULT_CHUNK = None   # edges per work item (longer segments - hubs - are split and summed in a second pass); None: by graph size
 SPMM_CHUNK = 512       # the same for the SpMM plans (64-byte rows: as tuned in round 1)
 SPMM_GROUP_BELOW = 64  # SpMM rows shorter than this run one per C/4-lane group (a group walks its row alone, four gathers in flight)
@@ -48,10 +50,10 @@ def auto_plan(E, H=None):
     return 256, 32, 32
 
 
-SMALL_STEPS = int(__import__("os").environ.get("MMA_SMALL_STEPS", "16"))
-SMALL_GROUP_BELOW = int(__import__("os").environ.get("MMA_SMALL_GROUP", "8"))
-SMALL_T_GROUP_BELOW = int(__import__("os").environ.get("MMA_SMALL_T_GROUP", str(SMALL_GROUP_BELOW)))
-ONE_LAUNCH = __import__("os").environ.get("MMA_ONE_LAUNCH", "1") != "0"
+SMALL_STEPS = integer("MMA_SMALL_STEPS", 16)
+SMALL_GROUP_BELOW = integer("MMA_SMALL_GROUP", 8)
+SMALL_T_GROUP_BELOW = integer("MMA_SMALL_T_GROUP", SMALL_GROUP_BELOW)
+ONE_LAUNCH = flag("MMA_ONE_LAUNCH")
 
 
 

@@ -22,8 +22,6 @@ from ._lib import require_gpu
 from .graph import DEFAULT_CHUNK, NCGraph, SpmmGraph
 from .scalers import SCALERS, scaler_row_factor, true_degree_row_factor
 
-FOLD_ROW_FACTOR = __import__("os").environ.get("MMA_FOLD_ROW_FACTOR", "1") != "0"
-
 # aggregator name -> (combine kind, raw logits under activation == "new_sigmoid")   layers.py:201-728
 _AGG = {
     "sum": ("sum", False), "sum2": ("sum", False), "sum3": ("sum", False), "sum4": ("sum", False),
@@ -246,9 +244,6 @@ class MMA(Module):
         msum = self._aggregate_all(self.aggregator_names, input, reduce_k=True)
         if self._sg is None or self._sg[0] is not adj:   # extension: a ready-made SpmmGraph is accepted as `adj`
             self._sg = (adj, adj if isinstance(adj, SpmmGraph) else SpmmGraph.from_torch_sparse(adj, input.device))
-        if not FOLD_ROW_FACTOR:
-            support = mm(msum, self.weight) * self._scaler_factor(N, input.device)
-            return Fn.csr_spmm(support, self.bias, self._sg[1], 1)              # layers.py:861-867
         # the row factor is a constant of the graph: it rides on the SpMM's edge values (A_ij * c_j), forward and transposed, instead of
         # an element-wise launch each way
         factor = self._scaler_factor(N, input.device)

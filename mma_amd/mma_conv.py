@@ -24,12 +24,13 @@ from torch.nn import ModuleList, ReLU, Sequential
 
 from . import dense
 from . import functional as Fn
+from ._env import flag
 from ._lib import require_gpu
 from .mask_aggr import MaskAggregateLinear
 from .pyg_compat import Linear, reset
 
 _SCATTER_REDUCE = ("sum", "mean", "min", "max")
-FACTOR_SCALERS = __import__("os").environ.get("MMA_FACTOR_SCALERS", "1") != "0"     # 0: materialise `out` (N,T,S*K*F) as in round 2
+FACTOR_SCALERS = flag("MMA_FACTOR_SCALERS")     # 0: materialise `out` (N,T,S*K*F) as in round 2
 
 
 class CategoricalEdges:
@@ -170,9 +171,8 @@ class _EdgeFold(torch.autograd.Function):
         return gWe, gWenc, gbenc
 
 
-EDGE_FOLD = __import__("os").environ.get("MMA_EDGE_FOLD", "1") != "0"
-PACK_WEIGHTS = __import__("os").environ.get("MMA_PACK_WEIGHTS", "1") != "0"
-ACCUMULATE_UNREGISTERED = __import__("os").environ.get("MMA_ACC_UNREGISTERED", "1") != "0"
+PACK_WEIGHTS = flag("MMA_PACK_WEIGHTS")
+ACCUMULATE_UNREGISTERED = flag("MMA_ACC_UNREGISTERED")
 
 
 class MMAConv(torch.nn.Module):
@@ -353,7 +353,7 @@ class MMAConv(torch.nn.Module):
                 # The (E, edge_dim) rows are put in target-sorted position order BEFORE the GEMM (50 floats per edge), so that Z
                 # - and in backward the (E, T*Fw) message gradients - stream contiguously through K3/K4.
                 We, enc = (packed[2] if packed else rows(2 * Fi, 3 * Fi)), self.edge_encoder
-                if (EDGE_FOLD and enc.bias is not None and We.is_cuda and We.dtype == torch.float32 and max(We.shape[1], enc.weight.shape[1]) <= 512
+                if (enc.bias is not None and We.is_cuda and We.dtype == torch.float32 and max(We.shape[1], enc.weight.shape[1]) <= 512
                         and enc.weight.dtype == torch.float32):
                     wz, bz = _EdgeFold.apply(We, enc.weight, enc.bias)                   # K19: one launch each way
                 else:

@@ -5,6 +5,7 @@ import torch
 import torch.nn.functional as F
 from torch.nn import BatchNorm1d, Embedding, Linear, ModuleList, ReLU, Sequential
 
+from ._env import flag
 from .mma_conv import CategoricalEdges, MMAConv
 
 
@@ -137,7 +138,7 @@ def masked_bn_relu(x, bn, n_valid):
     return F.relu(masked_batch_norm(x, bn, n_valid))
 
 
-FUSED_BN = __import__("os").environ.get("MMA_FUSED_BN", "1") != "0"
+FUSED_BN = flag("MMA_FUSED_BN")
 
 
 class Net(torch.nn.Module):

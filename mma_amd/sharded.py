@@ -22,13 +22,14 @@ import torch.distributed as dist
 
 from . import functional as Fn
 from .dense import mm, mm_into, rows_mm_add_, xt_g
+from ._env import flag
 from ._lib import call, ptr, require_gpu, stream_ptr
 from .graph import DEFAULT_CHUNK, NCGraph, SpmmGraph
 from .layers import _AGG
 from .scalers import scaler_row_factor, true_degree_row_factor
 
 
-DEVICE_PLAN = __import__("os").environ.get("MMA_DEVICE_PLAN", "1") != "0"     # 0: the host numpy plan builders (round 2)
+DEVICE_PLAN = flag("MMA_DEVICE_PLAN")     # 0: the host numpy plan builders (round 2)
 
 
 def partition_bounds(rowptr, world, row_cost=0.0):

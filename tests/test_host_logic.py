@@ -185,3 +185,30 @@ def test_weight_plan_table_reproduces_the_torch_plumbing(towers, F, edge_dim):
         for r in range(rows):
             hits[start + r * lda:start + r * lda + cols] += 1
     assert hits.min() == 1 and hits.max() == 1
+
+
+def test_every_environment_switch_is_documented_and_every_switch_a_test_sets_is_read():
+    """(a) every MMA_* name the package reads (mma_amd/_env.py's flag / integer, os.environ, getenv in csrc) is listed in README.md;
+    (b) every MMA_* name a test sets (monkeypatch.setenv, a child's environment) is read by the package, bench.py or the tests -
+    a test that sets a variable nothing reads compares one form with itself."""
+    import glob
+    quoted = re.compile(r'"(MMA_[A-Z0-9_]+)"')
+    reads = re.compile(r"\b(?:flag|integer|getenv)\(|\benviron\b")
+
+    def read_names(paths):
+        return {n for p in paths for line in open(p, errors="replace") if reads.search(line) for n in quoted.findall(line)}
+
+    package = [p for p in glob.glob(os.path.join(ROOT, "mma_amd", "**", "*.py"), recursive=True)]
+    package += [p for p in glob.glob(os.path.join(ROOT, "mma_amd", "csrc", "*")) if p.endswith((".hip", ".h", ".cpp"))]
+    read = read_names(package)
+    assert {"MMA_POST_ORDER", "MMA_ONE_LAUNCH", "MMA_MIN_ROWS_TN", "MMA_BINDING"} <= read, "the scan no longer finds the reads"
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    assert not [n for n in sorted(read) if not re.search(r"\b%s\b" % n, readme)], "read by the package, missing in README.md"
+
+    tests = glob.glob(os.path.join(ROOT, "tests", "*.py"))
+    read |= read_names(tests + [os.path.join(ROOT, "bench.py")])
+    sets = re.compile(r'setenv\(\s*"(MMA_[A-Z0-9_]+)"|env\w*\[\s*"(MMA_[A-Z0-9_]+)"\s*\]\s*=|[(,]\s*(MMA_[A-Z0-9_]+)\s*=')
+    this = os.path.abspath(__file__)
+    set_by_tests = {n for p in tests if os.path.abspath(p) != this for m in sets.finditer(open(p).read()) for n in m.groups() if n}
+    assert {"MMA_POST_ORDER", "MMA_POST_EXACT", "MMA_TN_PACKX"} <= set_by_tests, "the scan no longer finds what the tests set"
+    assert not sorted(set_by_tests - read), "set by a test, read by nothing"

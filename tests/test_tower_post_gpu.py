@@ -277,19 +277,20 @@ def test_k13_on_bf16_pieces_and_on_fp32_agree_with_float64(N, T, KF, O, scalers,
 
 
 def test_tower_post_results_do_not_depend_on_the_workgroup_order(monkeypatch):
-    """[r4] post_block(): the tower is the fastest-varying workgroup coordinate (whole agg rows are read / written by the workgroups that run
-    together); MMA_POST_TOWER_MAJOR=1 is round 3's order.  The arithmetic of a (tower, node block) does not know which workgroup id it has:
-    K13, K14 and K15 bit-equal in both orders, on the bf16-piece and the fp32 forward."""
+    """post_block() maps a workgroup id to its (tower, node block): MMA_POST_ORDER (read per call) = 0 XCD-grouped [r5], 1 tower-major
+    (round 3), 2 tower-fastest (round 4; K15's default).  The arithmetic of a (tower, node block) does not know which workgroup id it has:
+    K13, K14 and K15 bit-equal in all three orders, on the bf16-piece and the fp32 forward."""
     N, T, KF, O, scalers = 2500, 5, 152, 15, SC[:1] + SC[1:2] + SC[3:4]
     deg, rowptr, agg, Wo, cot = _post_case(N, T, KF, O, scalers, 7)
     for exact in ("0", "1"):
         monkeypatch.setenv("MMA_POST_EXACT", exact)
-        monkeypatch.setenv("MMA_POST_TOWER_MAJOR", "0")
-        a = _post_run(agg, Wo, rowptr, scalers, cot)
-        monkeypatch.setenv("MMA_POST_TOWER_MAJOR", "1")
-        b = _post_run(agg, Wo, rowptr, scalers, cot)
-        for x, y, what in zip(a, b, ("y", "gagg", "gWo")):
-            assert torch.equal(x, y), (what, exact)
+        runs = {}
+        for order in ("0", "1", "2"):
+            monkeypatch.setenv("MMA_POST_ORDER", order)
+            runs[order] = _post_run(agg, Wo, rowptr, scalers, cot)
+        for order in ("1", "2"):
+            for x, y, what in zip(runs["0"], runs[order], ("y", "gagg", "gWo")):
+                assert torch.equal(x, y), (what, "exact=" + exact, "order %s differs from order 0" % order)
 
 
 @pytest.mark.parametrize("N,fin,pitch", [(5000, 75, 75), (4099, 50, 64), (33000, 127, 127), (1, 3, 3), (2000, 76, 380)])

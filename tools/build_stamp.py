@@ -10,7 +10,7 @@ Round 4: kernel traffic also depends on the host-side planners and s
                no library is loadable the tree's own value is used and `library` says so
   host_sha     SHA-256 over the Python planners whose choices change what the kernels move (graph.py: chunking / grouping,
                functional.py, layers.py, mma_conv.py, dense.py, sharded.py)
-  env          the MMA_* switches in effect (SMALL_* / ONE_LAUNCH / FUSE_NODE_BWD / FACTOR_SCALERS / FOLD_ROW_FACTOR ... are all MMA_* variables)
+  env          the MMA_* switches in effect (SMALL_* / ONE_LAUNCH / FUSE_NODE_BWD / FACTOR_SCALERS / DEVICE_PLAN ... are all MMA_* variables; README.md lists them)
   stale_build  True when the loaded library was built from other sources than the tree holds
 
     python tools/build_stamp.py                # prints the stamp (JSON)

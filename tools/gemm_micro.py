@@ -5,8 +5,7 @@ C5 shard shape (H = 256, K = 8: 4096 wide), as the layer calls them (mma_amd.den
 MFMA work of its three piece products, and both roofline fractions (HBM 8.0 TB/s; fp16 MFMA 2.5 PFLOP/s dense).
 
     python tools/gemm_micro.py [--shape c4|c5|both] [--rounds 7] [--json]        (on the GPU box)
-A/B of a build switch: run it once per environment (e.g. MMA_DX_ACC=atomic) in the SAME gpurun call - the switches are read once
-per process."""
+A/B of a switch: run it once per environment (e.g. MMA_DX_NLP=0) back to back on the same box - the switches are read once per process."""
 import argparse
 import json
 import os

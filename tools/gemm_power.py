@@ -37,7 +37,7 @@ def main():
         dx = ((lambda: dense.gemm_f16x2_n128(g, rm, Wt, out, accumulate=True)) if dense.f16x2_n128_ok(N, 2 * K * H, H)
               else (lambda: dense.gemm_bf16x3(g, Wt, out=out, accumulate=True)))
         xm = x.abs().amax(1)                    # in the step the forward GEMM leaves this
-        three = dense.USE_F16X2 and dense.USE_F16X2_TN
+        three = dense.USE_F16X2
         tn = (lambda: dense.gemm_f16x2_tn(x, g, xm, rm)) if three else (lambda: dense.gemm_bf16x3_tn(x, g))
         for _ in range(2):                      # second pass: clocks settled
             r = (timed(lambda: dense.gemm_bf16x3(x, W)), timed(dx), timed(tn), timed(lambda: dense.gemm_bf16x3_tn(x, g)))
