@@ -111,6 +111,7 @@ CONFIGS = [
     (64, 260, 3, 70, ["sum", "mean", "max", "min", "sum2", "mean2", "max2", "min2"], "new_sigmoid", 0.5, 16),  # K=8, H>256
     (200, 32, 5, 100, ["sum", "mean", "max", "min", "sum2"], "sigmoid", 0.5, 48),   # K=5 -> slices 4+1
     (150, 20, 4, 0, ["sum", "mean", "max", "min", "softmin", "mean4", "max4"], "new_sigmoid", 0.0, 512),  # K=7
+    (180, 12, 4, 60, ["sum", "mean", "max", "min", "softmax", "softmin"], "sigmoid", 0.5, 32),       # K=6 -> slices 4+2, with edges and a hub
     # round 5: probabilities that are no multiple of 1/256 (16-bit thresholds, kernels' HASH16 form): vector + hub, scalar path, K=8, slices 4+1
     (300, 128, 6, 700, ["sum", "mean", "max", "min"], "new_sigmoid", 0.6, 256),
     (120, 75, 5, 90, ["sum3", "max2", "softmax"], "sigmoid", 0.3, 32),
