@@ -500,7 +500,9 @@ extern "C" int mma_csr_spmm_items(const int32_t* col, const float* val, const fl
               "C=%d ldb=%lld ldo=%lld n_items=%lld unsupported", C, (long long)ldb, (long long)ldo, (long long)n_items);
   MMA_REQUIRE(n_slots == 0 || (partial && hubs && n_hubs > 0), "hub slots without partial/hubs buffers");
   if (n_items == 0) return 0;
-  MMA_REQUIRE(B && out && items && al16(items) && (!hubs || al16(hubs)), "NULL or misaligned argument");
+  // no column array = no stored element: B is never read and may be NULL (the transposed product of a matrix without rows: a zero-row
+  // cotangent has no address), the items are all empty and every output row is written as bias or 0
+  MMA_REQUIRE((B || !col) && out && items && al16(items) && (!hubs || al16(hubs)), "NULL or misaligned argument");
   const bool v4 = (C % 4 == 0) && (ldb % 4 == 0) && (ldo % 4 == 0) && al16(B) && al16(out) && (!bias || al16(bias)) &&
                   (!partial || al16(partial));
   const int vec = v4 ? 4 : 1;
