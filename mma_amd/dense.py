@@ -1,10 +1,13 @@
-"""Dense pre/post transforms of the hot path: plain library GEMMs (rocBLAS / hipBLASLt fp32 MFMA through torch.mm),
-with one MI355X-specific twist in backward.
+"""Dense pre/post transforms of the hot path.  Tall products run on the split-precision GEMMs of csrc/gemm_x3.hip (three fp16 x 2 or six
+bf16 x 3 piece products per fp32 one): nn_form() / tn_form() are the ONE place where a shape meets its kernel, also for whoever must know the
+answer ahead of the call (a pad width, a row-maxima buffer).  The rest are library GEMMs (rocBLAS / hipBLASLt fp32 MFMA), with one twist:
 
 The weight gradients are (in, N) @ (N, out) products whose reduction dimension is the node count (1 M at C4) and whose
 output is tiny (128 x 512): a single GEMM call leaves most of the 256 CUs idle (measured 49-75 TFLOP/s, and 3.4 TFLOP/s
 for the (128,N)@(N,16) tail).  Splitting the reduction into ~N/8192 batches (strided-batched GEMM + a sum over the
 batch) fills the chip: 140 TFLOP/s, 89 % of the fp32 MFMA peak (0.97 ms instead of 2.7 ms per mask-weight half)."""
+from functools import partial
+
 import torch
 
 from . import _lib
@@ -17,37 +20,110 @@ def _span(name, nbytes=0, flops=0, mfma=None):
     return Fn._span(name, nbytes, flops, mfma)
 
 _ROWS_PER_BATCH = 8192
-USE_BF16X3 = True     # fp32-accurate GEMM on the bf16 matrix cores (csrc/gemm_x3.hip) where the shape allows
 _MIN_ROWS_X3 = 4096
 _MIN_COLS_TN = integer("MMA_MIN_COLS_TN", 1)
 _MIN_ROWS_TN = integer("MMA_MIN_ROWS_TN", 1024)    # the TN kernel from here on (Cora's 2 708 rows: the library's 128 x 256 x 2708 TN
                                                    # product takes 22-25 us, a fifth of the layer replay)
-
-
-def _x3_ok(a, w):
-    """The kernel takes K == 128 with any N, or any K % 128 == 0 with N <= 128 (accumulator tiles live in registers); a
-    product with both K > 128 and N > 128 (hidden width 256: C5) is run as N/128 column blocks of the second form."""
-    K, N = w.shape
-    return (USE_BF16X3 and a.is_cuda and a.dtype == torch.float32 and w.dtype == torch.float32 and a.shape[0] >= _MIN_ROWS_X3
-            and N % 32 == 0 and K % 128 == 0 and (K == 128 or N <= 128 or N % 128 == 0))
-
-
-USE_F16X2 = True      # K == 128 products on the three-product fp16 x 2 kernel (csrc/gemm_x3.hip) instead of the six-product bf16 x 3 one
-
-
+_MIN_ROWS_F16X2 = 1 << 16    # the three-product forms that take their row maxima from outside want tall inputs
+USE_F16X2 = True             # the three-product fp16 x 2 kernels where the shape allows, instead of the six-product bf16 x 3 ones
 F16X2_K = (64, 96, 128)      # reduction widths of the whole-row three-product kernel (mma_gemm_f16x2_k)
+PACK_K256 = flag("MMA_PACK_K256")     # 0: round 4's K = 256 forward (fp32 rows split per column group)
+USE_NLP = flag("MMA_DX_NLP")          # round 4: the pipelined one-accumulator form (0: round 3's kernel)
+TN_KA256 = flag("MMA_TN_KA256")       # 0: 128-column blocks of x, one launch each (round 3)
 
 
-def gemm_f16x2(a, w, out=None, row_max_out=None):
-    """a (M,K) @ w (K,N), K in F16X2_K, N % 128 == 0: the three-product form (fp16 hi/lo pieces, power-of-two row and column scales).
-    row_max_out (M,): the kernel also leaves max |a[i,:]| there (it forms them for its row scales anyway)."""
-    M, K = a.shape
-    N = w.shape[1]
-    bt2, cu = _split_f16x2(w)
-    if out is None:
-        out = torch.empty((M, N), device=a.device, dtype=torch.float32)
-    with _span("gemm_x3_k128", nbytes=4 * M * (K + N), flops=2 * M * K * N, mfma="f16x3"):        # A in, C out (B is 0.5 MB)
-        call("mma_gemm_f16x2_k", ptr(a), a.stride(0), ptr(bt2), ptr(cu), ptr(out), out.stride(0), ptr(row_max_out), M, N, K, stream_ptr())
+# ---- shape -> form: pure functions of integers and of the switches above, which they read when called (bench.py and the tests set them)
+def _rows_form(K, N):
+    """Row maxima from outside: N in {128, 256} with K % 128 == 0 is ONE pass over `a` on the pipelined one-accumulator kernel (also
+    for N = 256 - hidden width 256, C5); other shapes one launch of the two-accumulator kernel per 128-column block."""
+    return "f16x2_nlp" if USE_NLP and N in (128, 256) and K % 128 == 0 and K >= 256 else "f16x2_n128"
+
+
+def nn_form(M, K, N, *, accumulate=False, row_max_known=False, out_ok=True, aligned=True, named=False):
+    """The key of _NN_RUN that out (M,N) (+)= a (M,K) @ w (K,N) runs on.  row_max_known: the caller brings max |a[i,:]| along; out_ok:
+    no `out` yet, or a GPU fp32 one with unit column stride; aligned: `a` is read in place (_gpu_f32(a, aligned=True)); named: the
+    caller asked for these kernels by name (gemm_bf16x3) - no admission, never "lib"."""
+    rows = USE_F16X2 and K > 128 and K % 64 == 0 and N % 128 == 0 and M >= _MIN_ROWS_F16X2
+    if accumulate and row_max_known and not named and out_ok and aligned and rows and N <= 512:      # the dL/dx shape
+        return _rows_form(K, N)
+    # the six-product kernel takes K == 128 with any N, or any K % 128 == 0 with N <= 128 (accumulator tiles live in registers); a
+    # product with both K > 128 and N > 128 (hidden width 256: C5) is run as N/128 column blocks of the second form
+    if not named and not (M >= _MIN_ROWS_X3 and N % 32 == 0 and K % 128 == 0 and (K == 128 or N <= 128 or N % 128 == 0)
+                          and (out_ok or not accumulate)):
+        return "lib"
+    if USE_F16X2 and not accumulate and out_ok:
+        if K in F16X2_K and N % 128 == 0 and N <= 4096 and M >= _MIN_ROWS_X3:
+            return "f16x2_k"
+        if rows and N > 128:      # hidden width 256 (C5): does not fit the whole-row form; the row maxima cost one pass over `a`
+            if K == 256 and N <= 4096:
+                return "f16x2_k256p" if PACK_K256 else "f16x2_k256"
+            return _rows_form(K, N)
+    return "bf16x3" if K == 128 or N <= 128 else "bf16x3_blocks"
+
+
+def f16x2_n128_ok(M, K, N):
+    """Does rows_mm_add_ take a three-product kernel once it is given a's row maxima?  The producer of `a` asks: it has to leave them."""
+    return nn_form(M, K, N, accumulate=True, row_max_known=True).startswith("f16x2")
+
+
+def _tn_cols(form, KA):
+    """Columns of x per launch: wider x (C5) goes in 128-column blocks, [r4] in 256-column ones on the three-product kernel (G read once)."""
+    return KA if KA <= 128 else (256 if form == "f16x2_tn" and TN_KA256 and KA % 256 == 0 else 128)
+
+
+def _tn_window_fits(M, KA, NC, pitch, batch=None):
+    """The TN kernels address one split's row range through a 32-bit buffer window: (rows per split) x (row pitch) must stay < 2 GB.
+    The library tells the number of splits through its workspace: one (KA, NC) tile per split and product."""
+    n_ws = (_lib.query("mma_gemm_bf16x3_tn_workspace_floats", M, KA, NC) if batch is None else
+            _lib.query("mma_gemm_bf16x3_tn_batched_workspace_floats", M, KA, NC, batch))
+    splits = max(1, n_ws // ((batch or 1) * KA * NC))
+    rows = -(-(-(-M // splits)) // 32) * 32
+    return (rows + 32) * pitch * 4 < 2 ** 31
+
+
+def tn_form(M, KA, NC, *, ldx, ldg, g_row_max_known=False, batch=None, named=False):
+    """The key of _TN_RUN that x (M,KA)^T @ g (M,NC) runs on (row pitches ldx, ldg; batch=B: B such products over column blocks of the
+    same rows in one launch, or what ONE of them takes).  Up to 128 x columns (any count: ragged tiles are guarded) or whole 128-column
+    blocks; any g width (graph regression's odd-width Linears: 75 x 76; the 3- / 7-class output weights of node classification: the
+    library's TN product takes 22 us on Cora, 80 us on PubMed).  Three products when the caller brings g's row maxima - a pass over
+    the wide operand would cost what the form saves -, else six."""
+    pitch = max(ldx, ldg)
+    if (batch is not None and M >= _MIN_ROWS_X3 and 8 <= KA <= 128 and NC >= 32 and pitch < (1 << 24)
+            and _tn_window_fits(M, KA, NC, pitch, batch)):
+        return "bf16x3_tn_batched"
+    if not named and not (M >= _MIN_ROWS_TN and (8 <= KA <= 128 or KA % 128 == 0) and NC >= _MIN_COLS_TN
+                          and _tn_window_fits(M, min(KA, 128), NC, pitch)):
+        return "lib"
+    return "f16x2_tn" if USE_F16X2 and g_row_max_known and M >= _MIN_ROWS_F16X2 else "bf16x3_tn"
+
+
+def _gpu_f32(*ts, unit_cols=False, aligned=False):
+    """GPU fp32 tensors - unit_cols: matrices with unit column stride; aligned: and a row pitch of whole float4s from a 16-byte base."""
+    return all(t.is_cuda and t.dtype == torch.float32 and (not (unit_cols or aligned) or t.stride(1) == 1)
+               and (not aligned or (t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0)) for t in ts)
+
+
+# ---- form -> runner: (a, w, out, accumulate, row_max, box) with `out` allocated; each states its span name and mfma kind ------------
+def _gemm_span(name, mfma, M, K, N, accumulate=False):
+    """A in once (algorithmic: column blocks re-read it; B is 0.5 MB), C out - and in, when accumulating.  TN: x and g in once."""
+    return _span(name, nbytes=4 * M * (K + (2 if accumulate else 1) * N), flops=2 * M * K * N, mfma=mfma)
+
+
+def _row_max(a, box, fill=True):
+    """(M,) max |a[i,:]| for a form that was not given them (fill=False: its own kernel fills the buffer); `box` hands them on."""
+    rm = row_absmax(a) if fill else torch.empty((a.shape[0],), device=a.device, dtype=torch.float32)
+    if box is not None:
+        box.append(rm)
+    return rm
+
+
+def row_absmax(a):
+    """max |a[i,:]| per row in one pass (mma_row_absmax); torch's a.abs().amax(1) is two kernels and a full-size temporary."""
+    M, C = a.shape
+    out = torch.empty((M,), device=a.device, dtype=torch.float32)
+    if a.stride(1) != 1:
+        a = a.contiguous()
+    call("mma_row_absmax", ptr(a), a.stride(0) if M > 1 else C, M, C, ptr(out), stream_ptr())
     return out
 
 
@@ -62,249 +138,171 @@ def _split_f16x2(w, plain_lo=False):
     return bt2, cu
 
 
-PACK_K256 = flag("MMA_PACK_K256")        # 0: round 4's K = 256 forward (fp32 rows split per column group)
-
-
-def f16x2_n128_ok(M, K, N):
-    return (USE_F16X2 and USE_BF16X3 and N % 128 == 0 and N <= 512 and K % 64 == 0 and K > 128 and M >= (1 << 16))
-
-
-def row_absmax(a):
-    """max |a[i,:]| per row in one pass (mma_row_absmax); torch's a.abs().amax(1) is two kernels and a full-size temporary."""
-    M, C = a.shape
-    out = torch.empty((M,), device=a.device, dtype=torch.float32)
-    if a.stride(1) != 1:
-        a = a.contiguous()
-    call("mma_row_absmax", ptr(a), a.stride(0) if M > 1 else C, M, C, ptr(out), stream_ptr())
+def gemm_f16x2(a, w, out=None, row_max_out=None):
+    """a (M,K) @ w (K,N), K in F16X2_K, N % 128 == 0: the three-product form (fp16 hi/lo pieces, power-of-two row and column scales).
+    row_max_out (M,): the kernel also leaves max |a[i,:]| there (it forms them for its row scales anyway)."""
+    (M, K), N = a.shape, w.shape[1]
+    bt2, cu = _split_f16x2(w)
+    if out is None:
+        out = torch.empty((M, N), device=a.device, dtype=torch.float32)
+    with _gemm_span("gemm_x3_k128", "f16x3", M, K, N):
+        call("mma_gemm_f16x2_k", ptr(a), a.stride(0), ptr(bt2), ptr(cu), ptr(out), out.stride(0), ptr(row_max_out), M, N, K, stream_ptr())
     return out
 
 
-USE_NLP = flag("MMA_DX_NLP")      # round 4: the pipelined one-accumulator form (0: round 3's kernel)
+def _run_f16x2_k256(a, w, out, accumulate, rm, box, packed=False):
+    """K = 256 (C5 forward, N = 4096) with the whole 256-deep B slab resident per column group: A is read once per group through L2,
+    not once per 128-column launch from HBM.  packed [r5]: A goes into fp16 fragment order first (one pass: row maxima, scale
+    exponents, both pieces) and the 32 column groups stop re-splitting its rows; else the row maxima take a pass."""
+    (M, K), N = a.shape, w.shape[1]
+    rm = _row_max(a, box, fill=not packed)
+    bt2, cu = _split_f16x2(w)
+    if packed:
+        ap = torch.empty((_lib.query("mma_pack_f16x2_k256_bytes", M),), device=a.device, dtype=torch.uint8)
+        sce = torch.empty((M,), device=a.device, dtype=torch.int32)
+        with _span("pack_f16x2", nbytes=8 * M * K, flops=0):
+            call("mma_pack_f16x2_k256", ptr(a), a.stride(0), M, ptr(ap), ptr(sce), ptr(rm), stream_ptr())
+    rows = (ptr(ap), ptr(sce)) if packed else (ptr(a), a.stride(0), ptr(rm))
+    with _gemm_span("gemm_x3_persist", "f16x3", M, K, N):
+        call("mma_gemm_f16x2_k256p" if packed else "mma_gemm_f16x2_k256", *rows, ptr(bt2), ptr(cu), ptr(out), out.stride(0), M, N, stream_ptr())
+    return out
 
 
-def gemm_f16x2_n128(a, row_max, w, out, accumulate=False):
-    """out (M,N) (+)= a (M,K) @ w (K,N), N a multiple of 128, on the three-product kernels; row_max (M,) >= max |a[i,:]| (0 for an
-    all-zero row).  N in {128, 256} with K % 128 == 0 takes the pipelined one-accumulator kernel (mma_gemm_f16x2_nlp: ONE pass over
-    `a`, also for N = 256 - hidden width 256, C5); other shapes one launch of the two-accumulator kernel per 128-column block."""
-    M, K = a.shape
-    N = w.shape[1]
-    if USE_NLP and N in (128, 256) and K % 128 == 0 and K >= 256 and out.stride(1) == 1:
-        bt2, cu = _split_f16x2(w, plain_lo=True)
-        with _span("gemm_x3_acc" if accumulate else "gemm_x3_persist", nbytes=4 * M * (K + (2 if accumulate else 1) * N), flops=2 * M * K * N, mfma="f16x3"):
-            call("mma_gemm_f16x2_nlp", ptr(a), a.stride(0), ptr(row_max), ptr(bt2), ptr(cu), ptr(out), out.stride(0), M, N, K,
-                 1 if accumulate else 0, stream_ptr())
-        return out
-    bt2, cu = _split_f16x2(w)                                            # (2, N, K), (N,)
-    # A in once (algorithmic: the column blocks of a wider output re-read it), C out - and in, when accumulating
-    with _span("gemm_x3_acc" if accumulate else "gemm_x3_persist", nbytes=4 * M * (K + (2 if accumulate else 1) * N), flops=2 * M * K * N, mfma="f16x3"):
+def _run_f16x2_rows(a, w, out, accumulate, rm, box, nlp=False):
+    (M, K), N = a.shape, w.shape[1]
+    if rm is None:
+        rm = _row_max(a, box)
+    bt2, cu = _split_f16x2(w, plain_lo=nlp)                              # (2, N, K), (N,)
+    with _gemm_span("gemm_x3_acc" if accumulate else "gemm_x3_persist", "f16x3", M, K, N, accumulate):
+        if nlp:
+            call("mma_gemm_f16x2_nlp", ptr(a), a.stride(0), ptr(rm), ptr(bt2), ptr(cu), ptr(out), out.stride(0), M, N, K, accumulate, stream_ptr())
         # (walking A in row slabs that stay in the Infinity Cache between the column blocks was measured at C5's forward shape -
         # 32 blocks over a 1 GB A: 11.3 -> 11.2 ms, i.e. the kernel, not the re-reads of A, is what the product costs)
-        for b in range(N // 128):
+        for b in range(0 if nlp else N // 128):
             blk = bt2[:, 128 * b:128 * b + 128].contiguous() if N > 128 else bt2
-            call("mma_gemm_f16x2_n128", ptr(a), a.stride(0), ptr(row_max), ptr(blk), ptr(cu[128 * b:]), ptr(out[:, 128 * b:]), out.stride(0), M, K,
-                 1 if accumulate else 0, stream_ptr())
+            call("mma_gemm_f16x2_n128", ptr(a), a.stride(0), ptr(rm), ptr(blk), ptr(cu[128 * b:]), ptr(out[:, 128 * b:]), out.stride(0), M, K,
+                 accumulate, stream_ptr())
     return out
 
 
-def rows_mm_add_scaled_(acc, a, w, row_max):
-    """acc += a @ w like rows_mm_add_, on the three-product kernel when the rows' maxima are known (row_max (M,) >= max |a[i,:]|,
-    as K2a / K2b leave them) and the shape is the dL/dx one; else the six-product / library path."""
-    if (row_max is not None and a.shape[0] > 0 and f16x2_n128_ok(a.shape[0], a.shape[1], w.shape[1]) and acc.stride(1) == 1
-            and a.stride(1) == 1 and a.stride(0) % 4 == 0 and a.data_ptr() % 16 == 0):
-        return gemm_f16x2_n128(a, row_max, w, acc, accumulate=True)
-    return rows_mm_add_(acc, a, w)
-
-
-def gemm_bf16x3(a, w, out=None, accumulate=False, row_max_box=None):
-    """a (M,K) @ w (K,N) with fp32 accuracy on the bf16 MFMA path (three-piece split of both operands).  `a` may be a
-    row-strided view (a column block of a wider buffer); accumulate=True adds the product to `out`.  row_max_box: a list that
-    receives the (M,) row maxima of |a| when the path taken forms them anyway (the three-product forms)."""
-    if a.stride(1) != 1 or a.stride(0) % 4 or a.data_ptr() % 16:
-        a = a.contiguous()
-    M, K = a.shape
-    N = w.shape[1]
-    if (USE_F16X2 and K in F16X2_K and not accumulate and N % 128 == 0 and N <= 4096 and M >= _MIN_ROWS_X3
-            and (out is None or (out.stride(1) == 1 and out.dtype == torch.float32))):
-        rm = torch.empty((M,), device=a.device, dtype=torch.float32) if row_max_box is not None else None
-        if rm is not None:
-            row_max_box.append(rm)
-        return gemm_f16x2(a, w, out, rm)
-    if (USE_F16X2 and not accumulate and K > 128 and N > 128 and K % 64 == 0 and N % 128 == 0 and M >= (1 << 16)
-            and (out is None or (out.stride(1) == 1 and out.dtype == torch.float32))):
-        # hidden width 256 (C5): K = 256 does not fit the whole-row form of mma_gemm_f16x2; the chunked three-product kernel
-        # takes the row maxima from one cheap pass over `a` (M x K floats read against M x N written)
-        if out is None:
-            out = torch.empty((M, N), device=a.device, dtype=torch.float32)
-        if K == 256 and N <= 4096 and PACK_K256:
-            # [r5] A packed once into fp16 fragment order (one pass: row maxima, scale exponents, both pieces) - the 32 column groups of
-            # hidden width 256 stop re-loading the rows in the MFMA's fragment shape and re-splitting them (C5 shard: 7.7 -> see DESIGN.md)
-            rm = torch.empty((M,), device=a.device, dtype=torch.float32)
-            if row_max_box is not None:
-                row_max_box.append(rm)
-            ap = torch.empty((int(_lib.query("mma_pack_f16x2_k256_bytes", M)),), device=a.device, dtype=torch.uint8)
-            sce = torch.empty((M,), device=a.device, dtype=torch.int32)
-            bt2, cu = _split_f16x2(w)
-            with _span("pack_f16x2", nbytes=8 * M * K, flops=0):
-                call("mma_pack_f16x2_k256", ptr(a), a.stride(0), M, ptr(ap), ptr(sce), ptr(rm), stream_ptr())
-            with _span("gemm_x3_persist", nbytes=4 * M * (K + N), flops=2 * M * K * N, mfma="f16x3"):
-                call("mma_gemm_f16x2_k256p", ptr(ap), ptr(sce), ptr(bt2), ptr(cu), ptr(out), out.stride(0), M, N, stream_ptr())
-            return out
-        rm = row_absmax(a)
-        if row_max_box is not None:
-            row_max_box.append(rm)
-        if K == 256 and N <= 4096:
-            # column-group form with the whole 256-deep B slab resident: A is read once per column group through L2 instead of once per
-            # 128-column launch from HBM (C5 forward, N = 4096: 32 launches of the chunked kernel)
-            bt2, cu = _split_f16x2(w)
-            with _span("gemm_x3_persist", nbytes=4 * M * (K + N), flops=2 * M * K * N, mfma="f16x3"):
-                call("mma_gemm_f16x2_k256", ptr(a), a.stride(0), ptr(rm), ptr(bt2), ptr(cu), ptr(out), out.stride(0), M, N, stream_ptr())
-            return out
-        return gemm_f16x2_n128(a, rm, w, out)
+def _run_bf16x3(a, w, out, accumulate, rm, box, blocks=False):
+    (M, K), N = a.shape, w.shape[1]
     wt = w.t().contiguous()                                  # (N,K): B^T, k contiguous
     bt3 = torch.empty((3, N, K), device=a.device, dtype=torch.bfloat16)
     call("mma_split_bf16x3", ptr(wt), N * K, ptr(bt3), stream_ptr())
-    assert out is not None or not accumulate
-    if out is None:
-        out = torch.empty((M, N), device=a.device, dtype=torch.float32)
-    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.float32
-    acc = 1 if accumulate else 0
-    with _span("gemm_x3_acc" if accumulate else ("gemm_x3_k128" if K == 128 else "gemm_x3_persist"),
-               nbytes=4 * M * (K + (2 if accumulate else 1) * N), flops=2 * M * K * N, mfma="bf16x6"):
-        if K == 128 or N <= 128:
-            call("mma_gemm_bf16x3", ptr(a), a.stride(0), ptr(bt3), ptr(out), out.stride(0), M, N, K, acc, stream_ptr())
-        else:                                                # K > 128 and N > 128: one launch per 128-column block of the output
-            blocks = bt3.view(3, N // 128, 128, K).permute(1, 0, 2, 3).contiguous()    # (N/128, 3, 128, K): a block's own three pieces
-            for b in range(N // 128):
-                call("mma_gemm_bf16x3", ptr(a), a.stride(0), ptr(blocks[b]), ptr(out[:, 128 * b:128 * b + 128]), out.stride(0), M, 128,
-                     K, acc, stream_ptr())
+    with _gemm_span("gemm_x3_acc" if accumulate else "gemm_x3_k128" if K == 128 else "gemm_x3_persist", "bf16x6", M, K, N, accumulate):
+        n = 128 if blocks else N                             # blocks: one launch per 128-column block of the output
+        bt3 = bt3.view(3, N // n, n, K).permute(1, 0, 2, 3).contiguous()            # (N/n, 3, n, K): a block's own three pieces
+        for b in range(N // n):
+            call("mma_gemm_bf16x3", ptr(a), a.stride(0), ptr(bt3[b]), ptr(out[:, n * b:n * b + n]), out.stride(0), M, n, K, accumulate, stream_ptr())
     return out
+
+
+def _run_lib(a, w, out, accumulate, rm, box):
+    """The library GEMM.  A tall product into a new tensor is issued as a strided-batched GEMM over row blocks (w broadcast): rocBLAS
+    then picks a kernel that runs 15-25 % faster than the single tall-skinny GEMM (C4: 94 -> 114 TFLOP/s forward, 105 -> 135
+    TFLOP/s for g @ W^T)."""
+    (M, K), N = a.shape, w.shape[1]
+    B = M // _ROWS_PER_BATCH
+    if out is not None and not accumulate:
+        return torch.mm(a, w, out=out)
+    if accumulate and B >= 4:
+        return out.add_(_nn(a, w))
+    with _gemm_span("lib_mm", "f32", M, K, N, accumulate):      # rocBLAS fp32
+        if accumulate or B < 4:                 # accumulating: the library GEMM adds in its epilogue (beta = 1) - one launch, not two
+            return out.addmm_(a, w) if accumulate else torch.mm(a, w)
+        a = a.contiguous()
+        n = B * _ROWS_PER_BATCH
+        out = torch.empty((M, N), device=a.device, dtype=a.dtype)
+        torch.bmm(a[:n].view(B, _ROWS_PER_BATCH, -1), w.unsqueeze(0).expand(B, -1, -1), out=out[:n].view(B, _ROWS_PER_BATCH, -1))
+        if n < M:
+            torch.mm(a[n:], w, out=out[n:])
+        return out
+
+
+_NN_RUN = {"f16x2_k": lambda a, w, out, accumulate, rm, box: gemm_f16x2(a, w, out, _row_max(a, box, fill=False) if box is not None else None),
+           "f16x2_k256p": partial(_run_f16x2_k256, packed=True), "f16x2_k256": _run_f16x2_k256,
+           "f16x2_nlp": partial(_run_f16x2_rows, nlp=True), "f16x2_n128": _run_f16x2_rows,
+           "bf16x3": _run_bf16x3, "bf16x3_blocks": partial(_run_bf16x3, blocks=True), "lib": _run_lib}
+
+
+def _nn(a, w, out=None, accumulate=False, row_max=None, box=None, named=False):
+    """out (+)= a (M,K) @ w (K,N), no autograd: select the form, run it."""
+    M, N = a.shape[0], w.shape[1]
+    if M == 0 and out is not None:
+        return out
+    aligned = _gpu_f32(a, aligned=True)
+    form = "lib" if not (named or _gpu_f32(a, w)) else nn_form(
+        M, a.shape[1], N, accumulate=accumulate, row_max_known=row_max is not None,
+        out_ok=out is None or _gpu_f32(out, unit_cols=True), aligned=aligned, named=named)
+    if form != "lib":
+        a = a if aligned else a.contiguous()
+        assert not accumulate if out is None else (out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.float32)
+        out = out if out is not None else torch.empty((M, N), device=a.device, dtype=torch.float32)
+    return _NN_RUN[form](a, w, out, accumulate, row_max, box)
+
+
+def gemm_bf16x3(a, w, out=None, accumulate=False, row_max_box=None):
+    """a (M,K) @ w (K,N) with fp32 accuracy on the split-precision kernels whatever M is (never the library): nn_form(named=True)
+    picks among them.  `a` may be a row-strided view (a column block of a wider buffer); accumulate=True adds the product to `out`.
+    row_max_box: a list that receives the (M,) row maxima of |a| when the form taken forms them anyway (the three-product ones)."""
+    return _nn(a, w, out, accumulate, box=row_max_box, named=True)
+
+
+def gemm_f16x2_n128(a, row_max, w, out, accumulate=False):
+    """out (M,N) (+)= a (M,K) @ w (K,N), N a multiple of 128, on the three-product kernels that take the row maxima from outside
+    (_rows_form picks); row_max (M,) >= max |a[i,:]| (0 for an all-zero row)."""
+    return _NN_RUN[_rows_form(a.shape[1], w.shape[1])](a, w, out, accumulate, row_max, None)
 
 
 def mm_into(a, w, out, row_max_box=None):
     """out[...] = a @ w (no autograd): the forward GEMMs of the sharded layer write row blocks of one buffer.  row_max_box: see
     gemm_bf16x3 (stays empty when the path taken does not form the row maxima of a)."""
-    if a.shape[0] == 0:
-        return out
-    if _x3_ok(a, w):
-        return gemm_bf16x3(a, w, out, row_max_box=row_max_box)
-    return torch.mm(a, w, out=out)
+    return _nn(a, w, out, box=row_max_box)
 
 
-def rows_mm(a, w):
-    """a @ w for tall a, no autograd (bf16x3 kernel or row-batched library GEMM)."""
-    return _rows_mm(a, w)
-
-
-def rows_mm_add_(acc, a, w):
-    """acc += a @ w in place (no autograd): the bf16x3 kernel folds the addition into its epilogue."""
-    if a.shape[0] == 0:
-        return acc
-    if _x3_ok(a, w) and acc.stride(1) == 1:
-        return gemm_bf16x3(a, w, acc, accumulate=True)
-    if a.shape[0] // _ROWS_PER_BATCH < 4:                  # small: the library GEMM adds in its epilogue (beta = 1) - one launch, not two
-        with _span("lib_mm", nbytes=4 * a.shape[0] * (a.shape[1] + 2 * w.shape[1]), flops=2 * a.shape[0] * a.shape[1] * w.shape[1], mfma="f32"):
-            return acc.addmm_(a, w)
-    return acc.add_(_rows_mm(a, w))
-
-
-def _rows_mm(a, w):
-    """a (N,in) @ w (in,out) for tall a, issued as a strided-batched GEMM over row blocks (w broadcast): rocBLAS then
-    picks a kernel that runs 15-25 % faster than the single tall-skinny GEMM (C4: 94 -> 114 TFLOP/s forward,
-    105 -> 135 TFLOP/s for g @ W^T)."""
-    if _x3_ok(a, w):
-        return gemm_bf16x3(a, w)
-    N = a.shape[0]
-    B = N // _ROWS_PER_BATCH
-    with _span("lib_mm", nbytes=4 * N * (a.shape[1] + w.shape[1]), flops=2 * N * a.shape[1] * w.shape[1], mfma="f32"):      # rocBLAS fp32
-        if B < 4:
-            return torch.mm(a, w)
-        a = a.contiguous()
-        n = B * _ROWS_PER_BATCH
-        out = torch.empty((N, w.shape[1]), device=a.device, dtype=a.dtype)
-        torch.bmm(a[:n].view(B, _ROWS_PER_BATCH, -1), w.unsqueeze(0).expand(B, -1, -1), out=out[:n].view(B, _ROWS_PER_BATCH, -1))
-        if n < N:
-            torch.mm(a[n:], w, out=out[n:])
-        return out
+def rows_mm_add_(acc, a, w, row_max=None):
+    """acc += a @ w in place (no autograd): the split-precision kernels fold the addition into their epilogue.  On a three-product one
+    when the rows' maxima are known (row_max (M,) >= max |a[i,:]|, as K2a / K2b leave them) and the shape is the dL/dx one."""
+    return _nn(a, w, acc, accumulate=True, row_max=row_max)
 
 
 class _MM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w):
         ctx.save_for_backward(x, w)
-        return _rows_mm(x, w)
+        return _nn(x, w)
 
     @staticmethod
     def backward(ctx, g):
         x, w = ctx.saved_tensors
         gx = gw = None
         if ctx.needs_input_grad[0]:
-            gx = _rows_mm(g, w.t())
+            gx = _nn(g, w.t())
         if ctx.needs_input_grad[1]:
             gw = xt_g(x, g)
         return gx, gw
 
 
-def _x3_tn_ok(x, g):
-    """The kernel takes up to 128 x columns (any count: ragged tiles are guarded); wider x (hidden width 256: C5) runs as
-    128-column blocks of x.  Any g width (the odd-width Linear layers of graph regression: 75 x 76; the 3- / 7-class output
-    weights of node classification, where the library's TN product takes 22 us on Cora and 80 us on PubMed)."""
-    KA = x.shape[1]
-    ok = (USE_BF16X3 and x.is_cuda and x.dtype == torch.float32 and g.dtype == torch.float32 and x.shape[0] >= _MIN_ROWS_TN
-          and (8 <= KA <= 128 or KA % 128 == 0) and g.shape[1] >= _MIN_COLS_TN and x.stride(1) == 1 and g.stride(1) == 1)
-    if not ok:
-        return False
-    # the kernel addresses one row range through a 32-bit buffer window: (rows per split) x (row pitch) must stay < 2 GB
-    M, NC, kb = x.shape[0], g.shape[1], min(KA, 128)
-    splits = max(1, int(_lib.lib().mma_gemm_bf16x3_tn_workspace_floats(M, kb, NC)) // (kb * NC))
-    rows = -(-(-(-M // splits)) // 32) * 32
-    return (rows + 32) * max(x.stride(0), g.stride(0)) * 4 < 2 ** 31
-
-
-def gemm_bf16x3_tn(x, g):
-    """x^T @ g (in,out) for tall fp32 x (N,in), g (N,out) on the bf16x3 TN kernel (row-strided operands are fine)."""
-    N, KA = x.shape
-    NC = g.shape[1]
+def _run_tn(form, x, g, x_row_max=None, g_row_max=None):
+    """x^T @ g (in,out) for tall fp32 x (N,in), g (N,out) on mma_gemm_bf16x3_tn or mma_gemm_f16x2_tn (row-strided operands are fine).
+    The three-product kernel derives row scales balanced between the operands on the device from the row maxima ((N,) upper bounds of
+    max |x[i,:]| / max |g[i,:]|; None = one extra pass over that operand); rows too far apart in size send it to the six-product kernel."""
+    (N, KA), NC = x.shape, g.shape[1]
+    f16 = form == "f16x2_tn"
     out = torch.empty((KA, NC), device=x.device, dtype=torch.float32)
-    kb = KA if KA <= 128 else 128
-    n_ws = int(_lib.lib().mma_gemm_bf16x3_tn_workspace_floats(N, kb, NC))
+    kb = _tn_cols(form, KA)
+    n_ws = _lib.query("mma_gemm_%s_workspace_floats" % form, N, kb, NC)
     ws = torch.empty((n_ws,), device=x.device, dtype=torch.float32) if n_ws else None
-    with _span("gemm_x3_tn", nbytes=4 * N * (KA + NC), flops=2 * N * KA * NC, mfma="bf16x6"):
-        for j in range(0, KA, kb):                           # one launch per 128-column block of x (= row block of the result)
-            call("mma_gemm_bf16x3_tn", ptr(x[:, j:j + kb]), x.stride(0), ptr(g), g.stride(0), ptr(out[j:j + kb]), ptr(ws), n_ws, N, kb,
-                 NC, stream_ptr())
+    with _gemm_span("gemm_x3_tn", "f16x3" if f16 else "bf16x6", N, KA, NC):
+        for j in range(0, KA, kb):       # one launch per column block of x (= row block of the result); the maxima of the whole row bound every block's
+            call("mma_gemm_" + form, ptr(x[:, j:j + kb]), x.stride(0), ptr(g), g.stride(0), *((ptr(x_row_max), ptr(g_row_max)) if f16 else ()),
+                 ptr(out[j:j + kb]), ptr(ws), n_ws, N, kb, NC, stream_ptr())
     return out
 
 
-_MIN_ROWS_F16X2_TN = 1 << 16
-TN_KA256 = flag("MMA_TN_KA256")       # 0: 128-column blocks of x, one launch each (round 3)
-
-
-def gemm_f16x2_tn(x, g, x_row_max=None, g_row_max=None):
-    """x^T @ g like gemm_bf16x3_tn on the three-product fp16 x 2 kernel: row scales balanced between the operands, derived on
-    the device from the row maxima ((N,) upper bounds of max |x[i,:]| / max |g[i,:]|; None = one extra pass over that operand);
-    rows too far apart in size send the call to the six-product kernel (decided on the device)."""
-    N, KA = x.shape
-    NC = g.shape[1]
-    out = torch.empty((KA, NC), device=x.device, dtype=torch.float32)
-    # [r4] x up to 256 columns wide in ONE launch (hidden width 256: G is read once, not once per 128-column block of x)
-    kb = KA if KA <= 128 else (256 if TN_KA256 and KA % 256 == 0 else 128)
-    n_ws = int(_lib.lib().mma_gemm_f16x2_tn_workspace_floats(N, kb, NC))
-    ws = torch.empty((n_ws,), device=x.device, dtype=torch.float32)
-    with _span("gemm_x3_tn", nbytes=4 * N * (KA + NC), flops=2 * N * KA * NC, mfma="f16x3"):
-        for j in range(0, KA, kb):          # wider x (C5): 128-column blocks; the maxima of the whole row bound every block's
-            call("mma_gemm_f16x2_tn", ptr(x[:, j:j + kb]), x.stride(0), ptr(g), g.stride(0),
-                 ptr(x_row_max), ptr(g_row_max), ptr(out[j:j + kb]), ptr(ws), n_ws, N, kb,
-                 NC, stream_ptr())
-    return out
-
-
-def xt_g(x, g, x_row_max=None, g_row_max=None):
-    """x^T @ g for tall x (N,in), g (N,out): the TN kernels where the shape allows (three products when the caller brings g's row
-    maxima along - a pass over the wide operand would cost what the form saves -, else six), else split-N batched GEMM + sum."""
-    if _x3_tn_ok(x, g):
-        if USE_F16X2 and g_row_max is not None and x.shape[0] >= _MIN_ROWS_F16X2_TN:
-            return gemm_f16x2_tn(x, g, x_row_max, g_row_max)
-        return gemm_bf16x3_tn(x, g)
+def _lib_xt_g(x, g, x_row_max=None, g_row_max=None):
+    """Split-N batched library GEMM + sum (the module docstring)."""
     N = x.shape[0]
     B = N // _ROWS_PER_BATCH
     if B < 4:
@@ -318,22 +316,28 @@ def xt_g(x, g, x_row_max=None, g_row_max=None):
     return out
 
 
+gemm_f16x2_tn = partial(_run_tn, "f16x2_tn")                    # (x, g, x_row_max=None, g_row_max=None)
+gemm_bf16x3_tn = partial(_run_tn, "bf16x3_tn")                  # (x, g)
+_TN_RUN = {"f16x2_tn": gemm_f16x2_tn, "bf16x3_tn": gemm_bf16x3_tn, "lib": _lib_xt_g}
+
+
+def xt_g(x, g, x_row_max=None, g_row_max=None, named=False):
+    """x^T @ g for tall x (N,in), g (N,out): the TN kernels where tn_form allows (named: as in nn_form), else the library."""
+    form = "lib" if not (named or _gpu_f32(x, g, unit_cols=True)) else tn_form(
+        x.shape[0], x.shape[1], g.shape[1], ldx=x.stride(0), ldg=g.stride(0), g_row_max_known=g_row_max is not None, named=named)
+    return _TN_RUN[form](x, g, x_row_max, g_row_max)
+
+
 def xt_g_batched(x, ka, g, nc, B):
     """(B, ka, nc): out[b] = x[:, b*ka:(b+1)*ka]^T @ g[:, b*nc:(b+1)*nc] - B independent TN products over the same rows in ONE launch
     (mma_gemm_bf16x3_tn_batched) where the shape allows, else one xt_g per block."""
     M = x.shape[0]
-    ok = (USE_BF16X3 and x.is_cuda and x.dtype == torch.float32 and g.dtype == torch.float32 and M >= _MIN_ROWS_X3 and 8 <= ka <= 128
-          and nc >= 32 and x.stride(1) == 1 and g.stride(1) == 1 and max(x.stride(0), g.stride(0)) < (1 << 24))
-    if ok:
-        n_ws = int(_lib.lib().mma_gemm_bf16x3_tn_batched_workspace_floats(M, ka, nc, B))
-        splits = max(1, n_ws // (B * ka * nc))
-        rows = -(-(-(-M // splits)) // 32) * 32
-        ok = (rows + 32) * max(x.stride(0), g.stride(0)) * 4 < 2 ** 31          # one split's rows through a 32-bit buffer window
-    if not ok:
+    if not (_gpu_f32(x, g, unit_cols=True) and tn_form(M, ka, nc, ldx=x.stride(0), ldg=g.stride(0), batch=B) == "bf16x3_tn_batched"):
         return torch.stack([xt_g(x[:, b * ka:(b + 1) * ka], g[:, b * nc:(b + 1) * nc]) for b in range(B)])
     out = torch.empty((B, ka, nc), device=x.device, dtype=torch.float32)
+    n_ws = _lib.query("mma_gemm_bf16x3_tn_batched_workspace_floats", M, ka, nc, B)
     ws = torch.empty((n_ws,), device=x.device, dtype=torch.float32) if n_ws else None
-    with _span("gemm_x3_tn", nbytes=4 * M * B * (ka + nc), flops=2 * M * B * ka * nc, mfma="bf16x6"):
+    with _gemm_span("gemm_x3_tn", "bf16x6", M * B, ka, nc):
         call("mma_gemm_bf16x3_tn_batched", ptr(x), x.stride(0), ka, ptr(g), g.stride(0), nc, ptr(out), ptr(ws), n_ws, M, ka, nc, B,
              stream_ptr())
     return out
@@ -526,12 +530,12 @@ class _LinearX3(torch.autograd.Function):
         ctx.inv_index = inv_index
         fout = weight.shape[0]
         OP = _round_up(fout, 128)
-        fused = FUSED_PAD and x.is_cuda and x.dtype == torch.float32 and x.stride(1) == 1 and weight.dtype == torch.float32
+        fused = FUSED_PAD and _gpu_f32(x, unit_cols=True) and weight.dtype == torch.float32
         # [r5] the A operand is padded to 64 / 96 columns where [x | 1] fits (edge features 50 + 1, node features 75 + 1): the forward and
-        # the weight-gradient product stop reading, splitting and multiplying pad columns up to 128.  Only where gemm_bf16x3 hands the
-        # product to that kernel (its gate: OP <= 4096); the general kernel behind it takes K % 128 == 0 only
-        KP = (next(k for k in F16X2_K if fin + 1 <= k) if (USE_F16X2 and N >= _MIN_ROWS_X3 and OP <= 4096)
-              else 128)
+        # the weight-gradient product stop reading, splitting and multiplying pad columns up to 128 - where the forward product runs on the
+        # whole-row kernel: the general kernel behind it takes K % 128 == 0 only
+        KP = next(k for k in F16X2_K if fin + 1 <= k)
+        KP = KP if nn_form(N, KP, OP, named=True) == "f16x2_k" else 128
         if row_index is not None and not fused:
             x = x.index_select(0, row_index.long())
         if fused:
@@ -575,14 +579,12 @@ class _LinearX3(torch.autograd.Function):
         gx = gw = gb = None
         # [r5] the producer of g (K4 + the dV segment sum) left max |g row| with its padded buffer: both products take the THREE-product
         # fp16 x 2 kernels (round 4: six bf16 products, because nobody knew the row maxima - 15 % of the C2L step)
-        g_rm = getattr(gp, "_mma_row_max", None) if USE_F16X2 else None
-        three = g_rm is not None and xp.shape[0] >= _MIN_ROWS_F16X2_TN
+        g_rm = getattr(gp, "_mma_row_max", None)
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            KA = _round_up(fin + 1, 32)
-            gwb = gemm_f16x2_tn(xp[:, :KA], gp, ctx.x_rm, g_rm) if three else gemm_bf16x3_tn(xp[:, :KA], gp)   # (KA, OP) = [x | 1]^T g
+            gwb = xt_g(xp[:, :_round_up(fin + 1, 32)], gp, ctx.x_rm, g_rm, named=True)                 # (KA, OP) = [x | 1]^T g
             gw = gwb[:fin, :fout].t().contiguous()
             gb = gwb[fin, :fout].contiguous() if has_bias else None
-        if ctx.needs_input_grad[0] and three and wpad is not None and f16x2_n128_ok(gp.shape[0], OP, 128) and OP % 128 == 0 and OP >= 256:
+        if ctx.needs_input_grad[0] and g_rm is not None and wpad is not None and f16x2_n128_ok(gp.shape[0], OP, 128):
             # dL/dx = g [W | b | 0]: one pass over g on the one-accumulator kernel; column `fin` (the bias column) is dropped by the slice
             gx = gemm_f16x2_n128(gp, g_rm, wpad, torch.empty((gp.shape[0], 128), device=gp.device, dtype=torch.float32))[:, :fin]
         elif ctx.needs_input_grad[0]:
@@ -599,7 +601,7 @@ class _LinearX3(torch.autograd.Function):
 
 
 def linear_x3_ok(x, weight):
-    return (X3_LINEAR and USE_BF16X3 and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] >= X3_LINEAR_MIN_ROWS
+    return (X3_LINEAR and x.dim() == 2 and _gpu_f32(x) and x.shape[0] >= X3_LINEAR_MIN_ROWS
             and x.shape[1] + 1 <= 128 and weight.shape[0] > 128)      # narrower outputs: measured no better than the library (A is split per 4 tiles only)
 
 

@@ -217,17 +217,16 @@ class _NCLocalLayer(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .dense import rows_mm_add_, xt_g
+        from .dense import f16x2_n128_ok, rows_mm_add_, xt_g
         graph, kinds, acts, drop = ctx.graph, ctx.kinds, ctx.acts, ctx.drop
         x, PQ, T, sel, crow, wcat, x_row_max = ctx.saved_tensors
         N, H = x.shape
         K = len(kinds)
         KH = K * H
         g = g.contiguous()
-        from . import dense
         gPQ = torch.empty((N, 2 * KH), device=g.device, dtype=torch.float32)
         # the three-product dL/dx GEMM scales every row of [gP|gQ] by a power of two: K2a and K2b leave the row maxima here
-        row_max = torch.zeros((N,), device=g.device, dtype=torch.float32) if dense.f16x2_n128_ok(N, 2 * KH, H) and K <= 8 else None
+        row_max = torch.zeros((N,), device=g.device, dtype=torch.float32) if f16x2_n128_ok(N, 2 * KH, H) and K <= 8 else None
         gx = torch.empty((N, H), device=g.device, dtype=torch.float32)
         partial = (torch.empty((graph.t_n_slots, (K + 1) * H), device=g.device, dtype=torch.float32)
                    if graph.t_n_slots else None)
@@ -239,7 +238,7 @@ class _NCLocalLayer(torch.autograd.Function):
             gs, gP, gxs = nc_bwd_node_launch(g, True, sel, crow, T, graph, kinds, H, shared, gP=gPQ[:, :KH], row_max=row_max)
             nc_bwd_edges_launch(x, PQ[:, :KH], PQ[:, KH:], gs, g, crow, gxs, graph, kinds, acts, drop, gPQ[:, KH:], gx, partial,
                                 row_max=row_max)
-        dense.rows_mm_add_scaled_(gx, gPQ, wcat.t(), row_max)                # direct + through P and Q in one GEMM (C += A B)
+        rows_mm_add_(gx, gPQ, wcat.t(), row_max)                             # direct + through P and Q in one GEMM (C += A B)
         gw = xt_g(x, gPQ, x_row_max, row_max) if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) else None
         if ctx.cat_given:
             return gx, gw, None, None, None, None, None

@@ -438,7 +438,7 @@ class _ShardedAggregate(torch.autograd.Function):
         fuse = shared and Fn.FUSE_NODE_BWD          # K2a in the epilogue of the OWN-source launch (halo sources have no target role)
         gP = torch.empty((n, KH), device=dev, dtype=torch.float32)
         gQ = torch.empty((S, KH), device=dev, dtype=torch.float32)
-        from .dense import f16x2_n128_ok, rows_mm_add_scaled_
+        from .dense import f16x2_n128_ok, rows_mm_add_
         # row maxima of gP / gQ for the three-product dL/dx GEMMs (own rows: the larger of both; halo rows: gQ only)
         row_max = torch.zeros((S,), device=dev, dtype=torch.float32) if f16x2_n128_ok(max(n, S - n), KH, H) and K <= 8 else None
         gs = gxs = None
@@ -454,7 +454,7 @@ class _ShardedAggregate(torch.autograd.Function):
         if S > n:
             halo_part, own_part = graph.t_parts
             Fn.nc_bwd_edges_launch(x_src, P, Q, gs, g, crow, gxs, graph, kinds, acts, drop, gQ, gx, partial, halo_part, row_max=row_max, **epi)
-            gxh = rows_mm_add_scaled_(gx[n:], gQ[n:], wbot.t(), row_max[n:] if row_max is not None else None)   # halo rows: direct + via Q
+            gxh = rows_mm_add_(gx[n:], gQ[n:], wbot.t(), row_max[n:] if row_max is not None else None)   # halo rows: direct + via Q
             back = all_to_all_rows_start(gxh, plan.recv_counts, plan.send_counts, plan.group)
             Fn.nc_bwd_edges_launch(x_src, P, Q, gs, g, crow, gxs, graph, kinds, acts, drop, gQ, gx, partial, own_part, row_max=row_max, **epi)
         else:
@@ -462,8 +462,8 @@ class _ShardedAggregate(torch.autograd.Function):
                 back = all_to_all_rows_start(gx[n:], plan.recv_counts, plan.send_counts, plan.group)    # sends (0,H), still receives
             Fn.nc_bwd_edges_launch(x_src, P, Q, gs, g, crow, gxs, graph, kinds, acts, drop, gQ, gx, partial, row_max=row_max, **epi)
         rm_own = row_max[:n] if row_max is not None else None
-        gx_own = rows_mm_add_scaled_(gx[:n], gP, wtop.t(), rm_own)             # own rows: direct + through P ...
-        gx_own = rows_mm_add_scaled_(gx_own, gQ[:n], wbot.t(), rm_own)         # ... + through Q
+        gx_own = rows_mm_add_(gx[:n], gP, wtop.t(), rm_own)                    # own rows: direct + through P ...
+        gx_own = rows_mm_add_(gx_own, gQ[:n], wbot.t(), rm_own)                # ... + through Q
         gwtop = gwbot = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             rm = row_max                                          # K2b's row maxima also scale the three-product TN form

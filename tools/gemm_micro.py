@@ -46,10 +46,7 @@ def products(M, H, K):
     Wt = W.t()
     flops = 2.0 * M * H * W2
     fwd = lambda: dense.mm_into(x, W, out)
-    if dense.f16x2_n128_ok(M, W2, H):
-        dx = lambda: dense.gemm_f16x2_n128(gpq, rm, Wt, gx, accumulate=True)
-    else:
-        dx = lambda: dense.rows_mm_add_(gx, gpq, Wt)
+    dx = lambda: dense.rows_mm_add_(gx, gpq, Wt, rm)
     tn = lambda: dense.xt_g(x, gpq, xm, rm)
     return {
         "forward [P|Q] = x W (M,%d)x(%d,%d)" % (H, H, W2): (fwd, 4.0 * M * (H + W2), flops),

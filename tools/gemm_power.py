@@ -34,11 +34,9 @@ def main():
         x, W, g, Wt = mk(N, H), mk(H, 2 * K * H), mk(N, 2 * K * H), mk(2 * K * H, H)
         out = torch.zeros(N, H, device=DEV)
         rm = g.abs().amax(1)                    # in the step K2a / K2b produce this bound
-        dx = ((lambda: dense.gemm_f16x2_n128(g, rm, Wt, out, accumulate=True)) if dense.f16x2_n128_ok(N, 2 * K * H, H)
-              else (lambda: dense.gemm_bf16x3(g, Wt, out=out, accumulate=True)))
+        dx = lambda: dense.rows_mm_add_(out, g, Wt, rm)
         xm = x.abs().amax(1)                    # in the step the forward GEMM leaves this
-        three = dense.USE_F16X2
-        tn = (lambda: dense.gemm_f16x2_tn(x, g, xm, rm)) if three else (lambda: dense.gemm_bf16x3_tn(x, g))
+        tn = lambda: dense.xt_g(x, g, xm, rm)
         for _ in range(2):                      # second pass: clocks settled
             r = (timed(lambda: dense.gemm_bf16x3(x, W)), timed(dx), timed(tn), timed(lambda: dense.gemm_bf16x3_tn(x, g)))
         rows.append((name, r))
@@ -49,7 +47,9 @@ def main():
         print("| %s | %.3f ms | %.3f ms | %.3f ms | %.3f ms |" % ((name,) + r))
     rows = [(n, r[:3]) for n, r in rows]
     base = 2.0 * N * H * 2 * K * H                # fp32 flops of each product
-    mf = (3, 3 if dense.f16x2_n128_ok(N, 2 * K * H, H) else 6, 3 if three else 6) if dense.USE_F16X2 else (6, 6, 6)     # piece products per fp32 product
+    W2 = 2 * K * H                          # piece products per fp32 product: the forms that dense.py's selectors pick for the three calls
+    mf = tuple(3 if f.startswith("f16x2") else 6 for f in (dense.nn_form(N, H, W2, named=True), dense.nn_form(
+        N, W2, H, accumulate=True, row_max_known=True), dense.tn_form(N, H, W2, ldx=H, ldg=W2, g_row_max_known=True)))
     rate = lambda ts: " / ".join("%.2f" % (base * m / 1e15 / (t * 1e-3)) for t, m in zip(ts, mf))
     print("\nEach is 275 GFLOP of fp32 work = %s TFLOP of 16-bit MFMA (%s piece products per fp32 product); on random data that is %s "
           "PFLOP/s, on zeros %s PFLOP/s (dense bf16/fp16 peak 2.5 PFLOP/s at 2.4 GHz)." % (
