@@ -64,6 +64,9 @@ __device__ __forceinline__ Bf3 split3(const float v) {
   return r;
 }
 
+// Accumulator register r of a 32 x 32 MFMA tile holds row acc_row(r) + 4 h of the tile (h = lane >> 5), column lane & 31.
+__host__ __device__ constexpr int acc_row(int r) { return (r & 3) + 8 * (r >> 2); }
+
 template <int KC> struct SlabGeom {
   static constexpr int kRowPitch = KC * 2 + 16;   // bytes per LDS row: KC bf16 + 16 B pad (conflict-free ds_read_b128)
   static constexpr int kPiece = 32 * kRowPitch;   // one piece of one 32-column tile
@@ -157,7 +160,7 @@ __global__ __launch_bounds__(kBlock, 2) void gemm_x3_kernel(const GemmParams p, 
       if ((LAST_) && ACC) {                                                                         \
         const float* op = p.C + (size_t)((CT_) * 32 + r31);                                                  \
         _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                     \
-          const int64_t row = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;                                         \
+          const int64_t row = row0 + acc_row(r) + 4 * h;                                         \
           oldv[r] = (FULL || row < p.M) ? op[row * p.ldc] : 0.f;                                             \
         }                                                                                                    \
       }                                                                                                      \
@@ -178,16 +181,16 @@ __global__ __launch_bounds__(kBlock, 2) void gemm_x3_kernel(const GemmParams p, 
         const int nk = (it + 2) / n_ct;                                                                      \
         nxt = slab_load<KC>(p, tid, nk, it + 2 - nk * n_ct);                                                 \
       }                                                                                                      \
-      if (LAST_) { /* acc reg r holds row (r&3) + 8*(r>>2) + 4*h, column r31 of the tile */   \
+      if (LAST_) { /* acc reg r holds row acc_row(r) + 4*h, column r31 of the tile */   \
         float* cp = p.C + (size_t)((CT_) * 32 + r31);                                                        \
         if (ACC) {                                                                                           \
           _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                   \
-            const int64_t row = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;                                       \
+            const int64_t row = row0 + acc_row(r) + 4 * h;                                       \
             if (FULL || row < p.M) cp[row * p.ldc] = oldv[r] + C_[r];                                        \
           }                                                                                                  \
         } else {                                                                                             \
           _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                   \
-            const int64_t row = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;                                       \
+            const int64_t row = row0 + acc_row(r) + 4 * h;                                       \
             if (FULL || row < p.M) cp[row * p.ldc] = C_[r];                                                  \
           }                                                                                                  \
         }                                                                                                    \
@@ -333,7 +336,7 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_x3_colgroup_kernel(const G
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[r]), crow, c_off * 4u,
-                                              (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc + ct * 32) * 4u, kCgStoreAux);
+                                              (uint32_t)(acc_row(r) * (int)p.ldc + ct * 32) * 4u, kCgStoreAux);
     }
   }
 }
@@ -348,6 +351,38 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_x3_colgroup_kernel(const G
 // structure as gemm_x3_colgroup_kernel (resident B slab: 70 KB, pipelined fragments, nt buffer stores); handles a ragged M itself.
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 struct HFrag { f16x8 b1, b2; };
+
+// ---- the parts the fp16 x 2 kernels of this file share --------------------------------------------------------------------------------
+// log2 of a row's scale: the power of two that puts the row maximum into [2^14, 2^15), kept inside the fp32 exponent range
+__device__ __forceinline__ int row_scale_exp(const float rmax) {
+  const int ex = (int)((__float_as_uint(rmax) >> 23) & 0xFF);
+  return min(max(14 - (ex - 127), -126), 127);
+}
+__device__ __forceinline__ float exp2_f32(const int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
+// log2 of a column's un-scale (col_unscale holds exact powers of two)
+__device__ __forceinline__ int unscale_exp(const float u) { return (int)((__float_as_uint(u) >> 23) & 0xFF) - 127; }
+// eight floats under a scale -> their fp16 pieces: hi = fp16(x), lo = fp16((x - hi) 2^11); lo_arith = false is the measurement form "no
+// lo piece arithmetic" (lo = hi).  Returned BY VALUE: with reference parameters the pieces are built in memory first and the compiler
+// forms different (unpacked) conversions once the call is inlined - the device code is not the same.
+struct F16x2 { f16x8 hi, lo; };
+__device__ __forceinline__ F16x2 split_f16x2(const float4 a, const float4 b, const float sc, const bool lo_arith = true) {
+  const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  F16x2 r;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float x = v[i] * sc;
+    const _Float16 hi = (_Float16)x;
+    r.hi[i] = hi;
+    r.lo[i] = lo_arith ? (_Float16)((x - (float)hi) * 2048.f) : hi;
+  }
+  return r;
+}
+// Register r of a finished tile of the column-group kernels -> its row of C, streaming (nt): crow = descriptor of the wave's rows, c_off =
+// this lane's (4h, r31) in floats, pcol = the tile's first column in bytes.  Both the store behind a k-step and the final epilogue.
+__device__ __forceinline__ void cg_store(const float v, const __amdgpu_buffer_rsrc_t crow, const uint32_t c_off, const int r, const int ldc,
+                                         const uint32_t pcol) {
+  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), crow, c_off * 4u, (uint32_t)(acc_row(r) * ldc) * 4u + pcol, kCgStoreAux);
+}
 // [r5] KS k-steps of 16: K = 16 KS in {64, 96, 128}.  The B slab of a 128-column group is 2 pieces x 128 columns x (32 KS + 16) bytes - 68 KB at
 // K = 128, 36 KB at K = 64, 52 KB at K = 96 - so the narrow forms keep THREE groups resident (G2 = 3: 108 / 156 KB).
 template <int KS> struct HgGeom {
@@ -397,7 +432,7 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_kernel(cons
   // ONCE: a load inside the tile loop would sit behind the previous tile's 16 stores in the in-order vmcnt queue.
   int cues[NT];
 #pragma unroll
-  for (int t = 0; t < NT; ++t) cues[t] = (int)((__float_as_uint(col_unscale[g * 32 * NT + 32 * t + r31]) >> 23) & 0xFF) - 127;
+  for (int t = 0; t < NT; ++t) cues[t] = unscale_exp(col_unscale[g * 32 * NT + 32 * t + r31]);
   // the finished tile waiting to be stored (its stores ride between the next tile's MFMAs): values, descriptor, column offset.  Before the
   // first tile the descriptor covers ZERO bytes: the hardware's range check drops those stores, so the loop needs no "is there one" branch
   float prev[16];
@@ -436,15 +471,14 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_kernel(cons
     for (int i = 0; i < 2 * KS; ++i) rmax = fmaxf(rmax, fmaxf(fmaxf(fabsf(raw[i].x), fabsf(raw[i].y)), fmaxf(fabsf(raw[i].z), fabsf(raw[i].w))));
     rmax = fmaxf(rmax, __shfl_xor(rmax, 32, 64));
     if (a_row_max && g == 0 && h == 0 && r31 < rows_here) a_row_max[row0 + r31] = rmax;     // for the weight-gradient product (TN form)
-    const int ex = (int)((__float_as_uint(rmax) >> 23) & 0xFF);
-    const int sce = min(max(14 - (ex - 127), -126), 127);            // log2 of the row scale
-    const float sc = __uint_as_float((uint32_t)(sce + 127) << 23);
-    int rse[16];                                                   // accumulator register r holds row (r&3) + 8 (r>>2) + 4h: that row's
-#pragma unroll                                                     // scale exponent, fetched ONCE per block (not per tile and store)
-    for (int r = 0; r < 16; ++r) rse[r] = __shfl(sce, (r & 3) + 8 * (r >> 2) + 4 * h, 64);
+    const int sce = row_scale_exp(rmax);                             // log2 of the row scale
+    const float sc = exp2_f32(sce);
+    int rse[16];                                                   // the scale exponents of this lane's 16 tile rows, fetched ONCE per
+#pragma unroll                                                     // block (not per tile and store)
+    for (int r = 0; r < 16; ++r) rse[r] = __shfl(sce, acc_row(r) + 4 * h, 64);
     f16x8 af[KS][2];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
+    for (int ks = 0; ks < KS; ++ks) {       // split_f16x2 written out: through the helper the KS = 8 forms compile to other code (3-4 instructions)
       const float v[8] = {raw[2*ks].x, raw[2*ks].y, raw[2*ks].z, raw[2*ks].w, raw[2*ks+1].x, raw[2*ks+1].y, raw[2*ks+1].z, raw[2*ks+1].w};
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
@@ -495,16 +529,14 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_kernel(cons
 #pragma unroll
           for (int j = 0; j < SPK; ++j) {
             const int r = SPK * ks + j;
-            if (r < 16)
-              __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(prev[r]), crow_p, c_off * 4u,
-                                                    (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc) * 4u + pcol, kCgStoreAux);
+            if (r < 16) cg_store(prev[r], crow_p, c_off, r, (int)p.ldc, pcol);
           }
         } else {
           asm volatile("" :: "v"(prev[(2 * ks) & 15]), "v"(prev[(2 * ks + 1) & 15]));
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-      // row r of the tile belongs to lane-row (r&3)+8*(r>>2)+4h: its scale lives in the lane with that r31
+      // row acc_row(r) + 4h of the tile: its scale lives in the lane with that r31
 #pragma unroll
       for (int r = 0; r < 16; ++r) prev[r] = ldexpf(acc[r] + acl[r] * (1.f / 2048.f), cue - rse[r]);
       crow_p = crow;
@@ -513,9 +545,7 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_kernel(cons
   }
   // the last tile of the last unit
 #pragma unroll
-  for (int r = 0; r < 16; ++r)
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(prev[r]), crow_p, c_off * 4u, (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc) * 4u + pcol,
-                                          kCgStoreAux);
+  for (int r = 0; r < 16; ++r) cg_store(prev[r], crow_p, c_off, r, (int)p.ldc, pcol);
 }
 
 // ---- K == 256, three products (round 2, late): the forward [P|Q] = x [Wtop|Wbot] of hidden width 256 (C5) -----------------------------
@@ -526,7 +556,14 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_kernel(cons
 // once per column group through the XCD's L2 (the N/128 groups of one row stream share an XCD); the chunked N = 128 kernel, one
 // launch per 128 columns, re-read A from HBM 32 times at C5 (N = 4096).
 constexpr int kH2Pitch = 256 * 2 + 16, kH2Piece = 32 * kH2Pitch, kH2Tile = 2 * kH2Piece, kH2Lds = 4 * kH2Tile;      // 135 168 B
-__global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_k256_kernel(const GemmParams p, const float* row_max, const float* col_unscale,
+// One kernel for both forms of the A operand.  PACKED = false: A... = (row_max): fp32 rows p.A, loaded in fragment shape, scaled by the power
+// of two the caller's row maximum implies and split here.  PACKED = true: A... = (Ap, sce_arr) from mma_pack_f16x2_k256: one coalesced 1 KB
+// load per (k-step, piece), the scale exponent one read, no arithmetic on A.  Only that stage differs; a parameter pack (not a struct of
+// pointers) so that each form keeps the kernel arguments it had.
+template <class T, class... R> __device__ __forceinline__ T arg0(T t, R...) { return t; }
+template <class T, class U> __device__ __forceinline__ U arg1(T, U u) { return u; }
+template <bool PACKED, class... A>
+__global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_k256_kernel(const GemmParams p, A... a_operand, const float* col_unscale,
                                                                                 int64_t n_units, int n_groups) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kH2Lds];
   const int tid = threadIdx.x;
@@ -548,48 +585,67 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_k256_kernel
   const unsigned char* sb0 = lds + r31 * kH2Pitch + h * 16;
   int cues[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) cues[t] = (int)((__float_as_uint(col_unscale[g * 128 + 32 * t + r31]) >> 23) & 0xFF) - 127;
+  for (int t = 0; t < 4; ++t) cues[t] = unscale_exp(col_unscale[g * 128 + 32 * t + r31]);
   float prev[16];                                  // the finished tile whose stores ride between the next tile's MFMAs (zero-byte descriptor at first)
 #pragma unroll
   for (int r = 0; r < 16; ++r) prev[r] = 0.f;
   __amdgpu_buffer_rsrc_t crow_p = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, 0, 0x00020000);
   uint32_t pcol = 0;
+  // [r5, measured and NOT kept] (packed form) the next unit's fragments requested during the last tile of this one, each k-step's two pieces
+  // right behind the last MFMAs that read them (clean code: 192 MFMAs, four vmcnt waits per unit, no copies): 7.10 ms against 6.89 with the
+  // loads at the top of their own unit - the wait for the rows is not what this kernel loses its time to.
   for (int64_t u = stream; u < n_units; u += n_streams) {
     const int64_t row0 = u * kCgRows + wave * 32;
     if (row0 >= p.M) break;                                          // units ascend: every later one starts past M as well
     const int64_t rows_here = min((int64_t)32, p.M - row0);          // ragged last unit: rows past M re-read the last row, stores dropped
-    const int64_t myrow = row0 + min((int64_t)r31, rows_here - 1);
-    const float* ap = p.A + myrow * p.lda + 8 * h;
-    const float rmax = row_max[myrow];
-    const int ex = (int)((__float_as_uint(rmax) >> 23) & 0xFF);
-    const int sce = min(max(14 - (ex - 127), -126), 127);            // log2 of the row scale
-    const float sc = __uint_as_float((uint32_t)(sce + 127) << 23);
-    int rse[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) rse[r] = __shfl(sce, (r & 3) + 8 * (r >> 2) + 4 * h, 64);
-    f16x8 af[16][2];
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {                            // 16 float4 at a time: raw pieces turn into fp16 pieces in place
-      float4 raw[16];
+    f16x8 af[16][2];                                                 // the unit's A operand: 16 k-steps x 2 pieces, and
+    int rse[16];                                                     // the scale exponents of this lane's 16 tile rows
+    if constexpr (PACKED) {
+      const uint4* __restrict__ Ap = arg0(a_operand...);
+      const int* __restrict__ sce_arr = arg1(a_operand...);
+      const uint4* ap = Ap + (size_t)(row0 >> 5) * (16 * 2 * 64) + lane;
       if (kAbl & 8) {                                                 // measurement: no A loads
 #pragma unroll
-        for (int i = 0; i < 16; ++i) raw[i] = make_float4(rmax, 1.f, 1.f, 1.f);
+        for (int ks = 0; ks < 16; ++ks)
+#pragma unroll
+          for (int i = 0; i < 8; ++i) { af[ks][0][i] = (_Float16)1.f; af[ks][1][i] = (_Float16)0.5f; }
       } else {
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-          raw[2 * ks] = *reinterpret_cast<const float4*>(ap + (half * 8 + ks) * 16);
-          raw[2 * ks + 1] = *reinterpret_cast<const float4*>(ap + (half * 8 + ks) * 16 + 4);
+        for (int ks = 0; ks < 16; ++ks) {
+          const uint4 a0 = ap[(ks * 2 + 0) * 64], a1 = ap[(ks * 2 + 1) * 64];
+          af[ks][0] = *reinterpret_cast<const f16x8*>(&a0);
+          af[ks][1] = *reinterpret_cast<const f16x8*>(&a1);
         }
       }
+      const int sce = sce_arr[row0 + min((int64_t)r31, rows_here - 1)];
 #pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        const float v[8] = {raw[2*ks].x, raw[2*ks].y, raw[2*ks].z, raw[2*ks].w, raw[2*ks+1].x, raw[2*ks+1].y, raw[2*ks+1].z, raw[2*ks+1].w};
+      for (int r = 0; r < 16; ++r) rse[r] = __shfl(sce, acc_row(r) + 4 * h, 64);
+    } else {
+      const float* row_max = arg0(a_operand...);
+      const int64_t myrow = row0 + min((int64_t)r31, rows_here - 1);
+      const float* ap = p.A + myrow * p.lda + 8 * h;
+      const float rmax = row_max[myrow];
+      const int sce = row_scale_exp(rmax);                           // log2 of the row scale
+      const float sc = exp2_f32(sce);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float x = v[i] * sc;
-          const _Float16 hi = (_Float16)x;
-          af[half * 8 + ks][0][i] = hi;
-          af[half * 8 + ks][1][i] = (kAbl & 16) ? hi : (_Float16)((x - (float)hi) * 2048.f);      // 16: measurement, no lo piece arithmetic
+      for (int r = 0; r < 16; ++r) rse[r] = __shfl(sce, acc_row(r) + 4 * h, 64);
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {                          // 16 float4 at a time: raw pieces turn into fp16 pieces in place
+        float4 raw[16];
+        if (kAbl & 8) {                                               // measurement: no A loads
+#pragma unroll
+          for (int i = 0; i < 16; ++i) raw[i] = make_float4(rmax, 1.f, 1.f, 1.f);
+        } else {
+#pragma unroll
+          for (int ks = 0; ks < 8; ++ks) {
+            raw[2 * ks] = *reinterpret_cast<const float4*>(ap + (half * 8 + ks) * 16);
+            raw[2 * ks + 1] = *reinterpret_cast<const float4*>(ap + (half * 8 + ks) * 16 + 4);
+          }
+        }
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+          const F16x2 t = split_f16x2(raw[2 * ks], raw[2 * ks + 1], sc, !(kAbl & 16));      // 16: measurement, no lo piece arithmetic
+          af[half * 8 + ks][0] = t.hi; af[half * 8 + ks][1] = t.lo;
         }
       }
     }
@@ -616,6 +672,7 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_k256_kernel
         }
         __builtin_amdgcn_sched_barrier(0);
         if (!(kAbl & 2)) {
+          // (the hi product between the two lo products or behind them, with or without the scheduling fences: 6.92-6.99 ms, no difference)
           acl = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[ks][0], cur.b2, acl, 0, 0, 0);
           acl = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[ks][1], cur.b1, acl, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[ks][0], cur.b1, acc, 0, 0, 0);
@@ -625,8 +682,7 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_k256_kernel
         // [r4] one store of the PREVIOUS tile behind every k-step (see gemm_f16x2_colgroup_kernel): the 17 GB this product writes at
         // hidden width 256 leave in a steady stream beside the MFMAs instead of in bursts between them
         if (!(kAbl & 4))
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(prev[ks]), crow_p, c_off * 4u,
-                                                (uint32_t)(((ks & 3) + 8 * (ks >> 2)) * (int)p.ldc) * 4u + pcol, kCgStoreAux);
+          cg_store(prev[ks], crow_p, c_off, ks, (int)p.ldc, pcol);
         else
           asm volatile("" :: "v"(prev[ks]));
         __builtin_amdgcn_sched_barrier(0);
@@ -639,9 +695,7 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_k256_kernel
     }
   }
 #pragma unroll
-  for (int r = 0; r < 16; ++r)
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(prev[r]), crow_p, c_off * 4u, (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc) * 4u + pcol,
-                                          kCgStoreAux);
+  for (int r = 0; r < 16; ++r) cg_store(prev[r], crow_p, c_off, r, (int)p.ldc, pcol);      // the last tile of the last unit
 }
 
 // ---- [r5] K == 256 with a PACKED A operand ------------------------------------------------------------------------------------------
@@ -673,131 +727,17 @@ __global__ __launch_bounds__(256) void pack_f16x2_k256_kernel(const float* __res
 #pragma unroll
     for (int i = 0; i < 32; ++i) rmax = fmaxf(rmax, fmaxf(fmaxf(fabsf(raw[i].x), fabsf(raw[i].y)), fmaxf(fabsf(raw[i].z), fabsf(raw[i].w))));
     rmax = fmaxf(rmax, __shfl_xor(rmax, 32, 64));
-    const int ex = (int)((__float_as_uint(rmax) >> 23) & 0xFF);
-    const int sce = min(max(14 - (ex - 127), -126), 127);            // log2 of the row scale (the same rule as the kernels above)
-    const float sc = valid ? __uint_as_float((uint32_t)(sce + 127) << 23) : 0.f;      // rows past M: zero pieces
+    const int sce = row_scale_exp(rmax);
+    const float sc = valid ? exp2_f32(sce) : 0.f;                    // rows past M: zero pieces
     if (h == 0 && valid) { sce_out[row] = sce; if (row_max_out) row_max_out[row] = rmax; }
     uint4* dst = Ap + (size_t)u * (16 * 2 * 64) + lane;
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) {
-      const float v[8] = {raw[2*ks].x, raw[2*ks].y, raw[2*ks].z, raw[2*ks].w, raw[2*ks+1].x, raw[2*ks+1].y, raw[2*ks+1].z, raw[2*ks+1].w};
-      f16x8 hi8, lo8;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float x = v[i] * sc;
-        const _Float16 hi = (_Float16)x;
-        hi8[i] = hi;
-        lo8[i] = (_Float16)((x - (float)hi) * 2048.f);
-      }
-      dst[(ks * 2 + 0) * 64] = *reinterpret_cast<const uint4*>(&hi8);
-      dst[(ks * 2 + 1) * 64] = *reinterpret_cast<const uint4*>(&lo8);
+      const F16x2 t = split_f16x2(raw[2 * ks], raw[2 * ks + 1], sc);
+      dst[(ks * 2 + 0) * 64] = *reinterpret_cast<const uint4*>(&t.hi);
+      dst[(ks * 2 + 1) * 64] = *reinterpret_cast<const uint4*>(&t.lo);
     }
   }
-}
-
-__global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_k256p_kernel(const GemmParams p, const uint4* __restrict__ Ap,
-                                                                                 const int* __restrict__ sce_arr, const float* col_unscale,
-                                                                                 int64_t n_units, int n_groups) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[kH2Lds];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r31 = lane & 31, h = lane >> 5;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int streams_per_xcd = kCgSlotsPerXcd / n_groups;
-  if (slot >= streams_per_xcd * n_groups) return;
-  const int g = slot % n_groups;
-  const int64_t stream = xcd * streams_per_xcd + slot / n_groups, n_streams = 8 * streams_per_xcd;
-  const _Float16* Bh = reinterpret_cast<const _Float16*>(p.Bt);            // (2, N, 256) fp16: hi, lo * 2^11
-  for (int q = tid; q < 4 * 2 * 32 * 32; q += kCgThreads) {
-    const int kq = q & 31, col = (q >> 5) & 31, tp = q >> 10, piece = tp % 2, tile = tp / 2;
-    *reinterpret_cast<uint4*>(lds + tile * kH2Tile + piece * kH2Piece + col * kH2Pitch + kq * 16) =
-        *reinterpret_cast<const uint4*>(Bh + ((size_t)piece * p.N + (size_t)(g * 128 + tile * 32 + col)) * 256 + kq * 8);
-  }
-  __syncthreads();
-  const uint32_t c_off = 4u * h * (uint32_t)p.ldc + (uint32_t)r31;
-  const unsigned char* sb0 = lds + r31 * kH2Pitch + h * 16;
-  int cues[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) cues[t] = (int)((__float_as_uint(col_unscale[g * 128 + 32 * t + r31]) >> 23) & 0xFF) - 127;
-  float prev[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) prev[r] = 0.f;
-  __amdgpu_buffer_rsrc_t crow_p = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, 0, 0x00020000);
-  uint32_t pcol = 0;
-  // [r5, measured and NOT kept] the next unit's fragments requested during the last tile of this one, each k-step's two pieces right behind
-  // the last MFMAs that read them (clean code: 192 MFMAs, four vmcnt waits per unit, no copies): 7.10 ms against 6.89 with the loads at the
-  // top of their own unit - the wait for the rows is not what this kernel loses its time to.
-  for (int64_t u = stream; u < n_units; u += n_streams) {
-    const int64_t row0 = u * kCgRows + wave * 32;
-    if (row0 >= p.M) break;
-    const int64_t rows_here = min((int64_t)32, p.M - row0);
-    const uint4* ap = Ap + (size_t)(row0 >> 5) * (16 * 2 * 64) + lane;
-    f16x8 af[16][2];
-    if (kAbl & 8) {
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { af[ks][0][i] = (_Float16)1.f; af[ks][1][i] = (_Float16)0.5f; }
-    } else {
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) {
-        const uint4 a0 = ap[(ks * 2 + 0) * 64], a1 = ap[(ks * 2 + 1) * 64];
-        af[ks][0] = *reinterpret_cast<const f16x8*>(&a0);
-        af[ks][1] = *reinterpret_cast<const f16x8*>(&a1);
-      }
-    }
-    const int sce = sce_arr[row0 + min((int64_t)r31, rows_here - 1)];
-    int rse[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) rse[r] = __shfl(sce, (r & 3) + 8 * (r >> 2) + 4 * h, 64);
-    const __amdgpu_buffer_rsrc_t crow =
-        __builtin_amdgcn_make_buffer_rsrc(p.C + row0 * p.ldc, 0, (int)min((int64_t)0x7fffffff, rows_here * p.ldc * 4), 0x00020000);
-#pragma unroll 1
-    for (int ct = 0; ct < 4; ++ct) {
-      int cue = cues[0];
-#pragma unroll
-      for (int t = 1; t < 4; ++t) cue = ct == t ? cues[t] : cue;
-      f32x16 acc, acl;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acl[r] = 0.f; }
-      const unsigned char* sb = sb0 + ct * kH2Tile;
-      HFrag cur;
-      cur.b1 = *reinterpret_cast<const f16x8*>(sb);
-      cur.b2 = *reinterpret_cast<const f16x8*>(sb + kH2Piece);
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) {
-        HFrag nxt = cur;
-        if (ks < 15) {
-          nxt.b1 = *reinterpret_cast<const f16x8*>(sb + (ks + 1) * 32);
-          nxt.b2 = *reinterpret_cast<const f16x8*>(sb + kH2Piece + (ks + 1) * 32);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(kAbl & 2)) {
-          // (the hi product between the two lo products or behind them, with or without the scheduling fences: 6.92-6.99 ms, no difference)
-          acl = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[ks][0], cur.b2, acl, 0, 0, 0);
-          acl = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[ks][1], cur.b1, acl, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[ks][0], cur.b1, acc, 0, 0, 0);
-        } else {
-          asm volatile("" :: "v"(af[ks][0]), "v"(af[ks][1]), "v"(cur.b1), "v"(cur.b2));
-        }
-        if (!(kAbl & 4))
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(prev[ks]), crow_p, c_off * 4u,
-                                                (uint32_t)(((ks & 3) + 8 * (ks >> 2)) * (int)p.ldc) * 4u + pcol, kCgStoreAux);
-        else
-          asm volatile("" :: "v"(prev[ks]));
-        __builtin_amdgcn_sched_barrier(0);
-        cur = nxt;
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) prev[r] = ldexpf(acc[r] + acl[r] * (1.f / 2048.f), cue - rse[r]);
-      crow_p = crow;
-      pcol = (uint32_t)(g * 128 + ct * 32) * 4u;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r)
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(prev[r]), crow_p, c_off * 4u, (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc) * 4u + pcol,
-                                          kCgStoreAux);
 }
 
 // ---- N == 128, long K: the dL/dx products g [Wtop|Wbot]^T (round 2) ---------------------------------------------------
@@ -920,10 +860,10 @@ __global__ __launch_bounds__(kNlThreads, 1) void gemm_x3_n128_kernel(const GemmP
                    // result is the deterministic old + product).  Old values in registers cost 64 VGPRs (spills); starting the
                    // accumulators from them would round the old value once per MFMA instead of once.
           __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(acc[t][r], crow, c_off,
-                                                          (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc + t * 32) * 4u, 0);
+                                                          (uint32_t)(acc_row(r) * (int)p.ldc + t * 32) * 4u, 0);
         else
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[t][r]), crow, c_off,
-                                                (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc + t * 32) * 4u, 0);
+                                                (uint32_t)(acc_row(r) * (int)p.ldc + t * 32) * 4u, 0);
   }
 }
 
@@ -960,9 +900,8 @@ __global__ __launch_bounds__(kNlThreads, 1) void gemm_f16x2_n128_kernel(const Ge
     const float* ap = p.A + min(arow_i, p.M - 1) * p.lda + 8 * h;
     // power-of-two row scale from the caller's bound on the row maximum
     const float rmax = row_max[min(arow_i, p.M - 1)];
-    const int ex = (int)((__float_as_uint(rmax) >> 23) & 0xFF);
-    const int sce = min(max(14 - (ex - 127), -126), 127);
-    const float sc = __uint_as_float((uint32_t)(sce + 127) << 23);
+    const int sce = row_scale_exp(rmax);                             // log2 of the row scale
+    const float sc = exp2_f32(sce);
     f32x16 acc[4], acl[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -985,14 +924,8 @@ __global__ __launch_bounds__(kNlThreads, 1) void gemm_f16x2_n128_kernel(const Ge
       f16x8 af[4][2];
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        const float v[8] = {raw[2*ks].x, raw[2*ks].y, raw[2*ks].z, raw[2*ks].w, raw[2*ks+1].x, raw[2*ks+1].y, raw[2*ks+1].z, raw[2*ks+1].w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float x = v[i] * sc;
-          const _Float16 hi = (_Float16)x;
-          af[ks][0][i] = hi;
-          af[ks][1][i] = (_Float16)((x - (float)hi) * 2048.f);
-        }
+        const F16x2 t = split_f16x2(raw[2 * ks], raw[2 * ks + 1], sc);
+        af[ks][0] = t.hi; af[ks][1] = t.lo;
       }
       const bool more = kc + 1 < n_kc;
       if (more) {                                         // next chunk: slab and A, in flight during this chunk's MFMAs
@@ -1043,15 +976,15 @@ __global__ __launch_bounds__(kNlThreads, 1) void gemm_f16x2_n128_kernel(const Ge
       for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          oldv[t][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(crow, c_off, (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc + t * 32) * 4u, 0));
+          oldv[t][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(crow, c_off, (uint32_t)(acc_row(r) * (int)p.ldc + t * 32) * 4u, 0));
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const int cue = (int)((__float_as_uint(col_unscale[t * 32 + r31]) >> 23) & 0xFF) - 127;
+        const int cue = unscale_exp(col_unscale[t * 32 + r31]);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int rse = __shfl(sce, (r & 3) + 8 * (r >> 2) + 4 * h, 64);
+          const int rse = __shfl(sce, acc_row(r) + 4 * h, 64);
           const float val = ldexpf(acc[t][r] + acl[t][r] * (1.f / 2048.f), cue - rse);
-          const uint32_t so = (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc + t * 32) * 4u;
+          const uint32_t so = (uint32_t)(acc_row(r) * (int)p.ldc + t * 32) * 4u;
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(oldv[t][r] + val), crow, c_off, so, 0);
         }
       }
@@ -1059,12 +992,12 @@ __global__ __launch_bounds__(kNlThreads, 1) void gemm_f16x2_n128_kernel(const Ge
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const int cue = (int)((__float_as_uint(col_unscale[t * 32 + r31]) >> 23) & 0xFF) - 127;
+      const int cue = unscale_exp(col_unscale[t * 32 + r31]);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int rse = __shfl(sce, (r & 3) + 8 * (r >> 2) + 4 * h, 64);          // once per 256 x 128 block: not worth 16 registers
+        const int rse = __shfl(sce, acc_row(r) + 4 * h, 64);          // once per 256 x 128 block: not worth 16 registers
         const float val = ldexpf(acc[t][r] + acl[t][r] * (1.f / 2048.f), cue - rse);
-        const uint32_t so = (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc + t * 32) * 4u;
+        const uint32_t so = (uint32_t)(acc_row(r) * (int)p.ldc + t * 32) * 4u;
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), crow, c_off, so, 0);
       }
     }
@@ -1120,9 +1053,8 @@ __global__ __launch_bounds__(kNlThreads, 1) void gemm_f16x2_nlp_kernel(const Gem
     const uint32_t a_voff_rm = ((uint32_t)(lane >> 4) * (uint32_t)p.lda + 4u * (lane & 15)) * 4u;         // (measurement build 128)
     const float* abase = p.A + base_row * p.lda;                     // + chunk * 64 floats
     const float rmax = row_max[base_row + drow];
-    const int ex = (int)((__float_as_uint(rmax) >> 23) & 0xFF);
-    const int sce = min(max(14 - (ex - 127), -126), 127);
-    const float sc = __uint_as_float((uint32_t)(sce + 127) << 23);
+    const int sce = row_scale_exp(rmax);                             // log2 of the row scale
+    const float sc = exp2_f32(sce);
     f32x16 acc[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t)
@@ -1330,16 +1262,16 @@ __global__ __launch_bounds__(kNlThreads, 1) void gemm_f16x2_nlp_kernel(const Gem
         for (int t = 0; t < 4; ++t)
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            oldv[t][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(crow, c_off, (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc + (t0 + t) * 32) * 4u, 0));
+            oldv[t][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(crow, c_off, (uint32_t)(acc_row(r) * (int)p.ldc + (t0 + t) * 32) * 4u, 0));
       }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const int cue = (int)((__float_as_uint(col_unscale[(t0 + t) * 32 + r31]) >> 23) & 0xFF) - 127;
+        const int cue = unscale_exp(col_unscale[(t0 + t) * 32 + r31]);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int rse = __shfl(sce, (r & 3) + 8 * (r >> 2) + 4 * h, 64);
+          const int rse = __shfl(sce, acc_row(r) + 4 * h, 64);
           const float val = ldexpf(acc[t0 + t][r], cue - rse);
-          const uint32_t so = (uint32_t)(((r & 3) + 8 * (r >> 2)) * (int)p.ldc + (t0 + t) * 32) * 4u;
+          const uint32_t so = (uint32_t)(acc_row(r) * (int)p.ldc + (t0 + t) * 32) * 4u;
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ACC == 2 ? oldv[t][r] + val : val), crow, c_off, so, 0);
         }
       }
@@ -1588,8 +1520,8 @@ __global__ __launch_bounds__(kBlock, 2) void gemm_x3_tn_kernel(const TnParams p)
       if (ct < n_ct) {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (FULLCT || (wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h < p.KA && gcol0 + ct * 32 + r31 < p.NC))
-            out[(size_t)((r & 3) + 8 * (r >> 2) + 4 * h) * p.NC + ct * 32] = acc[ct][r];
+          if (FULLCT || (wave * 32 + acc_row(r) + 4 * h < p.KA && gcol0 + ct * 32 + r31 < p.NC))
+            out[(size_t)(acc_row(r) + 4 * h) * p.NC + ct * 32] = acc[ct][r];
       }
     }
   }
@@ -1920,8 +1852,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void gemm_f16x2_tn_kernel
       if (ct < n_ct) {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (FULLCT || (wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h < p.KA && gcol0 + ct * 32 + r31 < p.NC))
-            out[(size_t)((r & 3) + 8 * (r >> 2) + 4 * h) * p.NC + ct * 32] = ldexpf(acc[ct][r], ue);
+          if (FULLCT || (wave * 32 + acc_row(r) + 4 * h < p.KA && gcol0 + ct * 32 + r31 < p.NC))
+            out[(size_t)(acc_row(r) + 4 * h) * p.NC + ct * 32] = ldexpf(acc[ct][r], ue);
       }
     }
   }
@@ -1943,6 +1875,47 @@ static int tn_splits(int64_t M, int NC) {
 
 using namespace mma;
 
+// ---- host-side checks and plans the entry points share ----------------------------------------------------------------------------------
+constexpr int kGo = -1;               // "checks passed, go on": what the helpers below return instead of an entry point's result
+static bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+static int nn_pointers(const void* A, const void* Bt, bool others) {
+  MMA_REQUIRE(A && Bt && others && aligned16(A) && aligned16(Bt), "NULL or misaligned argument");
+  return kGo;
+}
+// What every NN entry point checks after its own shape, in this order: the row pitches (A at least min_lda wide), M == 0 (nothing to do:
+// 0, before any pointer is looked at), then the pointers (`others`: the remaining ones are non-NULL).
+static int nn_operands(const void* A, int64_t lda, int64_t min_lda, const void* Bt, bool others, int64_t ldc, int N, int64_t M) {
+  MMA_REQUIRE(lda >= min_lda && ldc >= N && lda % 4 == 0 && lda < (1 << 24) && ldc < (1 << 24), "row pitch too small, unaligned or >= 2^24");
+  if (M == 0) return 0;
+  return nn_pointers(A, Bt, others);
+}
+static int colgroup_shape(int64_t M, int N) {
+  MMA_REQUIRE(M >= 0 && N >= 128 && N % 128 == 0 && N / 128 <= kCgSlotsPerXcd, "M=%lld N=%d: need N %% 128 == 0, N <= 4096", (long long)M, N);
+  return kGo;
+}
+#define MMA_CHECKED(call) do { if (const int rc_ = (call); rc_ != kGo) return rc_; } while (0)
+
+// The TN forms cut the reduction over M into s row ranges of rps rows (whole chunks), one workgroup per range and 128-column block of G
+// (and batch entry); a range must fit the 2 GB window of a buffer descriptor.
+struct TnPlan { int64_t rps; dim3 grid; };
+static int tn_plan(int s, int64_t M, int64_t ldx, int64_t ldg, int NC, int B, TnPlan& pl) {
+  pl.rps = ((M + s - 1) / s + kTnKC - 1) / kTnKC * kTnKC;
+  MMA_REQUIRE((pl.rps + kTnKC) * (ldx > ldg ? ldx : ldg) * 4 < (1LL << 31), "row range of one split exceeds a 2 GB buffer window");
+  pl.grid = dim3((unsigned)(((NC + 127) / 128) * s), (unsigned)B);
+  return kGo;
+}
+static void launch_x3_tn(const TnParams& p, dim3 grid, hipStream_t st) {
+  if (p.NC % 128 == 0 && p.KA % 32 == 0) hipLaunchKernelGGL(gemm_x3_tn_kernel<true>, grid, dim3(kBlock), 0, st, p);
+  else hipLaunchKernelGGL(gemm_x3_tn_kernel<false>, grid, dim3(kBlock), 0, st, p);
+}
+template <int NW>
+static void launch_f16x2_tn(const TnParams& p, dim3 grid, hipStream_t st, bool full, bool px) {
+  if (px && full) hipLaunchKernelGGL((gemm_f16x2_tn_kernel<true, NW, true>), grid, dim3(64 * NW), 0, st, p);
+  else if (px) hipLaunchKernelGGL((gemm_f16x2_tn_kernel<false, NW, true>), grid, dim3(64 * NW), 0, st, p);
+  else if (full) hipLaunchKernelGGL((gemm_f16x2_tn_kernel<true, NW>), grid, dim3(64 * NW), 0, st, p);
+  else hipLaunchKernelGGL((gemm_f16x2_tn_kernel<false, NW>), grid, dim3(64 * NW), 0, st, p);
+}
+
 extern "C" int mma_split_bf16x3(const float* in, int64_t n, void* out, void* stream) {
   MMA_REQUIRE(n >= 0, "n < 0");
   if (n == 0) return 0;
@@ -1959,10 +1932,7 @@ extern "C" int mma_gemm_bf16x3(const float* A, int64_t lda, const void* Bt3, flo
   MMA_REQUIRE(M >= 0 && N >= 32 && K >= kKC && N % 32 == 0 && K % kKC == 0, "M=%lld N=%d K=%d: need N %% 32 == 0, K %% 128 == 0",
               (long long)M, N, K);
   MMA_REQUIRE(K == kKC || N <= 128, "either K == 128 or N <= 128 (accumulator tiles live in registers)");
-  MMA_REQUIRE(lda >= K && ldc >= N && lda % 4 == 0 && lda < (1 << 24) && ldc < (1 << 24), "row pitch too small, unaligned or >= 2^24");
-  if (M == 0) return 0;
-  MMA_REQUIRE(A && Bt3 && C && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(Bt3) & 15) == 0,
-              "NULL or misaligned argument");
+  MMA_CHECKED(nn_operands(A, lda, K, Bt3, C != nullptr, ldc, N, M));
   GemmParams p{A, lda, static_cast<const __bf16*>(Bt3), C, ldc, M, N, K, accumulate ? 1 : 0};
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nct = K == kKC ? 0 : N / 32;
@@ -2019,11 +1989,8 @@ extern "C" int mma_split_f16x2(const float* w, int64_t stride_k, int64_t stride_
 
 extern "C" int mma_gemm_f16x2(const float* A, int64_t lda, const void* Bt2, const float* col_unscale, float* C, int64_t ldc,
                               float* a_row_max, int64_t M, int32_t N, void* stream) {
-  MMA_REQUIRE(M >= 0 && N >= 128 && N % 128 == 0 && N / 128 <= kCgSlotsPerXcd, "M=%lld N=%d: need N %% 128 == 0, N <= 4096", (long long)M, N);
-  MMA_REQUIRE(lda >= 128 && ldc >= N && lda % 4 == 0 && lda < (1 << 24) && ldc < (1 << 24), "row pitch too small, unaligned or >= 2^24");
-  if (M == 0) return 0;
-  MMA_REQUIRE(A && Bt2 && col_unscale && C && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(Bt2) & 15) == 0,
-              "NULL or misaligned argument");
+  MMA_CHECKED(colgroup_shape(M, N));
+  MMA_CHECKED(nn_operands(A, lda, 128, Bt2, col_unscale && C, ldc, N, M));
   GemmParams p{A, lda, static_cast<const __bf16*>(Bt2), C, ldc, M, N, 128, 0};
   const int64_t n_units = (M + kCgRows - 1) / kCgRows;
   const int groups = N / 128;
@@ -2041,11 +2008,8 @@ extern "C" int mma_gemm_f16x2_k(const float* A, int64_t lda, const void* Bt2, co
                                 float* a_row_max, int64_t M, int32_t N, int32_t K, void* stream) {
   if (K == 128) return mma_gemm_f16x2(A, lda, Bt2, col_unscale, C, ldc, a_row_max, M, N, stream);
   MMA_REQUIRE(K == 64 || K == 96, "K=%d unsupported (64, 96 or 128)", K);
-  MMA_REQUIRE(M >= 0 && N >= 128 && N % 128 == 0 && N / 128 <= kCgSlotsPerXcd, "M=%lld N=%d: need N %% 128 == 0, N <= 4096", (long long)M, N);
-  MMA_REQUIRE(lda >= K && ldc >= N && lda % 4 == 0 && lda < (1 << 24) && ldc < (1 << 24), "row pitch too small, unaligned or >= 2^24");
-  if (M == 0) return 0;
-  MMA_REQUIRE(A && Bt2 && col_unscale && C && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(Bt2) & 15) == 0,
-              "NULL or misaligned argument");
+  MMA_CHECKED(colgroup_shape(M, N));
+  MMA_CHECKED(nn_operands(A, lda, K, Bt2, col_unscale && C, ldc, N, M));
   GemmParams p{A, lda, static_cast<const __bf16*>(Bt2), C, ldc, M, N, K, 0};
   const int64_t n_units = (M + kCgRows - 1) / kCgRows;
   const int groups = N / 128;
@@ -2061,14 +2025,11 @@ extern "C" int mma_gemm_f16x2_k(const float* A, int64_t lda, const void* Bt2, co
 
 extern "C" int mma_gemm_f16x2_k256(const float* A, int64_t lda, const float* row_max, const void* Bt2, const float* col_unscale, float* C,
                                    int64_t ldc, int64_t M, int32_t N, void* stream) {
-  MMA_REQUIRE(M >= 0 && N >= 128 && N % 128 == 0 && N / 128 <= kCgSlotsPerXcd, "M=%lld N=%d: need N %% 128 == 0, N <= 4096", (long long)M, N);
-  MMA_REQUIRE(lda >= 256 && ldc >= N && lda % 4 == 0 && lda < (1 << 24) && ldc < (1 << 24), "row pitch too small, unaligned or >= 2^24");
-  if (M == 0) return 0;
-  MMA_REQUIRE(A && row_max && Bt2 && col_unscale && C && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(Bt2) & 15) == 0,
-              "NULL or misaligned argument");
+  MMA_CHECKED(colgroup_shape(M, N));
+  MMA_CHECKED(nn_operands(A, lda, 256, Bt2, row_max && col_unscale && C, ldc, N, M));
   GemmParams p{A, lda, static_cast<const __bf16*>(Bt2), C, ldc, M, N, 256, 0};
   const int64_t n_units = (M + kCgRows - 1) / kCgRows;
-  hipLaunchKernelGGL(gemm_f16x2_colgroup_k256_kernel, dim3(256), dim3(kCgThreads), 0, static_cast<hipStream_t>(stream), p, row_max, col_unscale,
+  hipLaunchKernelGGL((gemm_f16x2_colgroup_k256_kernel<false, const float*>), dim3(256), dim3(kCgThreads), 0, static_cast<hipStream_t>(stream), p, row_max, col_unscale,
                      n_units, N / 128);
   return check_launch("gemm_f16x2_colgroup_k256_kernel");
 }
@@ -2087,25 +2048,21 @@ extern "C" int mma_pack_f16x2_k256(const float* A, int64_t lda, int64_t M, void*
 }
 extern "C" int mma_gemm_f16x2_k256p(const void* Ap, const int32_t* sce, const void* Bt2, const float* col_unscale, float* C, int64_t ldc,
                                     int64_t M, int32_t N, void* stream) {
-  MMA_REQUIRE(M >= 0 && N >= 128 && N % 128 == 0 && N / 128 <= kCgSlotsPerXcd, "M=%lld N=%d: need N %% 128 == 0, N <= 4096", (long long)M, N);
+  MMA_CHECKED(colgroup_shape(M, N));
   MMA_REQUIRE(ldc >= N && ldc < (1 << 24), "row pitch too small or >= 2^24");
   if (M == 0) return 0;
-  MMA_REQUIRE(Ap && sce && Bt2 && col_unscale && C && (reinterpret_cast<uintptr_t>(Ap) & 15) == 0 && (reinterpret_cast<uintptr_t>(Bt2) & 15) == 0,
-              "NULL or misaligned argument");
+  MMA_CHECKED(nn_pointers(Ap, Bt2, sce && col_unscale && C));        // (no A pitch: the packed operand has its own layout)
   GemmParams p{nullptr, 256, static_cast<const __bf16*>(Bt2), C, ldc, M, N, 256, 0};
   const int64_t n_units = (M + kCgRows - 1) / kCgRows;
-  hipLaunchKernelGGL(gemm_f16x2_colgroup_k256p_kernel, dim3(256), dim3(kCgThreads), 0, static_cast<hipStream_t>(stream), p,
+  hipLaunchKernelGGL((gemm_f16x2_colgroup_k256_kernel<true, const uint4* __restrict__, const int* __restrict__>), dim3(256), dim3(kCgThreads), 0, static_cast<hipStream_t>(stream), p,
                      static_cast<const uint4*>(Ap), sce, col_unscale, n_units, N / 128);
-  return check_launch("gemm_f16x2_colgroup_k256p_kernel");
+  return check_launch("gemm_f16x2_colgroup_k256_kernel (packed)");
 }
 
 extern "C" int mma_gemm_f16x2_n128(const float* A, int64_t lda, const float* row_max, const void* Bt2, const float* col_unscale, float* C,
                                    int64_t ldc, int64_t M, int32_t K, int32_t accumulate, void* stream) {
   MMA_REQUIRE(M >= 0 && K >= kNlKC && K % kNlKC == 0 && K <= (1 << 20), "M=%lld K=%d: need K %% 64 == 0", (long long)M, K);
-  MMA_REQUIRE(lda >= K && ldc >= 128 && lda % 4 == 0 && lda < (1 << 24) && ldc < (1 << 24), "row pitch too small, unaligned or >= 2^24");
-  if (M == 0) return 0;
-  MMA_REQUIRE(A && row_max && Bt2 && col_unscale && C && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(Bt2) & 15) == 0,
-              "NULL or misaligned argument");
+  MMA_CHECKED(nn_operands(A, lda, K, Bt2, row_max && col_unscale && C, ldc, 128, M));
   GemmParams p{A, lda, static_cast<const __bf16*>(Bt2), C, ldc, M, 128, K, accumulate ? 1 : 0};
   const int64_t n_units = (M + kNlRows - 1) / kNlRows;
   const dim3 g((unsigned)(n_units < 256 ? n_units : 256));
@@ -2119,10 +2076,7 @@ extern "C" int mma_gemm_f16x2_nlp(const float* A, int64_t lda, const float* row_
                                   int64_t ldc, int64_t M, int32_t N, int32_t K, int32_t accumulate, void* stream) {
   MMA_REQUIRE(M >= 0 && (N == 128 || N == 256) && K >= 4 * kNlKC && K % (2 * kNlKC) == 0 && K <= (1 << 20),
               "M=%lld N=%d K=%d: need N in {128, 256}, K %% 128 == 0, K >= 256", (long long)M, N, K);
-  MMA_REQUIRE(lda >= K && ldc >= N && lda % 4 == 0 && lda < (1 << 24) && ldc < (1 << 24), "row pitch too small, unaligned or >= 2^24");
-  if (M == 0) return 0;
-  MMA_REQUIRE(A && row_max && Bt2 && col_unscale && C && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(Bt2) & 15) == 0,
-              "NULL or misaligned argument");
+  MMA_CHECKED(nn_operands(A, lda, K, Bt2, row_max && col_unscale && C, ldc, N, M));
   GemmParams p{A, lda, static_cast<const __bf16*>(Bt2), C, ldc, M, N, K, accumulate ? 1 : 0};
   const int64_t n_units = (M + kNlRows - 1) / kNlRows;
   const dim3 g((unsigned)(n_units < 256 ? n_units : 256));
@@ -2152,14 +2106,10 @@ extern "C" int mma_gemm_bf16x3_tn(const float* X, int64_t ldx, const float* G, i
   const int s = tn_splits(M, NC);
   MMA_REQUIRE(s == 1 || (ws && ws_floats >= (int64_t)s * KA * NC), "workspace too small: %lld floats, need %lld",
               (long long)ws_floats, (long long)s * KA * NC);
-  int64_t rps = (M + s - 1) / s;
-  rps = (rps + kTnKC - 1) / kTnKC * kTnKC;
-  MMA_REQUIRE((rps + kTnKC) * (ldx > ldg ? ldx : ldg) * 4 < (1LL << 31), "row range of one split exceeds a 2 GB buffer window");
-  TnParams p{X, ldx, G, ldg, s == 1 ? C : ws, M, rps, KA, NC, s};
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)(((NC + 127) / 128) * s));
-  if (NC % 128 == 0 && KA % 32 == 0) hipLaunchKernelGGL(gemm_x3_tn_kernel<true>, grid, dim3(kBlock), 0, st, p);
-  else hipLaunchKernelGGL(gemm_x3_tn_kernel<false>, grid, dim3(kBlock), 0, st, p);
+  TnPlan pl;
+  MMA_CHECKED(tn_plan(s, M, ldx, ldg, NC, 1, pl));
+  TnParams p{X, ldx, G, ldg, s == 1 ? C : ws, M, pl.rps, KA, NC, s};
+  launch_x3_tn(p, pl.grid, static_cast<hipStream_t>(stream));
   if (int rc = check_launch("gemm_x3_tn_kernel")) return rc;
   if (s == 1) return 0;
   return mma_col_sum(ws, (int64_t)KA * NC, s, KA * NC, C, nullptr, 0, stream);      // <= 512 rows: one pass, fixed order
@@ -2191,15 +2141,11 @@ extern "C" int mma_gemm_bf16x3_tn_batched(const float* X, int64_t ldx, int64_t x
   const int s = tn_splits_batched(M, NC, B);
   MMA_REQUIRE(s == 1 || (ws && ws_floats >= (int64_t)s * B * KA * NC), "workspace too small: %lld floats, need %lld",
               (long long)ws_floats, (long long)s * B * KA * NC);
-  int64_t rps = (M + s - 1) / s;
-  rps = (rps + kTnKC - 1) / kTnKC * kTnKC;
-  MMA_REQUIRE((rps + kTnKC) * (ldx > ldg ? ldx : ldg) * 4 < (1LL << 31), "row range of one split exceeds a 2 GB buffer window");
-  TnParams p{X, ldx, G, ldg, s == 1 ? C : ws, M, rps, KA, NC, s};
+  TnPlan pl;
+  MMA_CHECKED(tn_plan(s, M, ldx, ldg, NC, B, pl));
+  TnParams p{X, ldx, G, ldg, s == 1 ? C : ws, M, pl.rps, KA, NC, s};
   p.xb = xb; p.gb = gb; p.part_ss = (int64_t)B * KA * NC;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)(((NC + 127) / 128) * s), (unsigned)B);
-  if (NC % 128 == 0 && KA % 32 == 0) hipLaunchKernelGGL(gemm_x3_tn_kernel<true>, grid, dim3(kBlock), 0, st, p);
-  else hipLaunchKernelGGL(gemm_x3_tn_kernel<false>, grid, dim3(kBlock), 0, st, p);
+  launch_x3_tn(p, pl.grid, static_cast<hipStream_t>(stream));
   if (int rc = check_launch("gemm_x3_tn_kernel (batched)")) return rc;
   if (s == 1) return 0;
   return mma_col_sum(ws, (int64_t)B * KA * NC, s, B * KA * NC, C, nullptr, 0, stream);      // <= 512 rows: one pass, fixed order
@@ -2243,9 +2189,10 @@ extern "C" int mma_gemm_f16x2_tn(const float* X, int64_t ldx, const float* G, in
   const bool px = tn_packx(M, KA, NC);
   const int64_t n_need = n_part + 3 * Mp + 4 + (px ? tn_packx_floats(M, KA) : 0);
   MMA_REQUIRE(ws_floats >= n_need, "workspace too small: %lld floats, need %lld", (long long)ws_floats, (long long)n_need);
-  int64_t rps = (M + s - 1) / s;
-  rps = (rps + kTnKC - 1) / kTnKC * kTnKC;
-  MMA_REQUIRE((rps + kTnKC) * (ldx > ldg ? ldx : ldg) * 4 < (1LL << 31), "row range of one split exceeds a 2 GB buffer window");
+  TnPlan pl;
+  MMA_CHECKED(tn_plan(s, M, ldx, ldg, NC, 1, pl));
+  const int64_t rps = pl.rps;
+  const dim3 grid = pl.grid;
   const int nb = (KA + 31) / 32;
   MMA_REQUIRE(!px || (rps / kTnKC + 1) * (int64_t)nb * 4096 < (1LL << 31), "packed rows of one split exceed a 2 GB buffer window");
   float* xmax = ws + n_part;
@@ -2262,7 +2209,6 @@ extern "C" int mma_gemm_f16x2_tn(const float* X, int64_t ldx, const float* G, in
   hipLaunchKernelGGL(tn_scale_rows_kernel, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, st, x_row_max, g_row_max, M, Mp, state, sxh, sgh);
   if (int rc = check_launch("tn_scale_rows_kernel")) return rc;
   TnParams p{X, ldx, G, ldg, s == 1 ? C : ws, M, rps, KA, NC, s, sxh, sgh, state, 0};
-  const dim3 grid((unsigned)(((NC + 127) / 128) * s));
   const bool full = NC % 128 == 0 && KA % 32 == 0;
   if (px) {
     u32x4* xp = reinterpret_cast<u32x4*>(ws + n_part + 3 * Mp + 4);
@@ -2271,25 +2217,14 @@ extern "C" int mma_gemm_f16x2_tn(const float* X, int64_t ldx, const float* G, in
                        xp, nb, n_items);
     p.xp = xp; p.xp_nb = nb;
   }
-  if (KA > 128) {                                                    // [r4] X up to 256 columns wide: eight waves on one staged G tile
-    if (px) { if (full) hipLaunchKernelGGL((gemm_f16x2_tn_kernel<true, 8, true>), grid, dim3(512), 0, st, p);
-              else hipLaunchKernelGGL((gemm_f16x2_tn_kernel<false, 8, true>), grid, dim3(512), 0, st, p); }
-    else if (full) hipLaunchKernelGGL((gemm_f16x2_tn_kernel<true, 8>), grid, dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((gemm_f16x2_tn_kernel<false, 8>), grid, dim3(512), 0, st, p);
-  } else {
-    if (px) { if (full) hipLaunchKernelGGL((gemm_f16x2_tn_kernel<true, 4, true>), grid, dim3(kBlock), 0, st, p);
-              else hipLaunchKernelGGL((gemm_f16x2_tn_kernel<false, 4, true>), grid, dim3(kBlock), 0, st, p); }
-    else if (full) hipLaunchKernelGGL((gemm_f16x2_tn_kernel<true, 4>), grid, dim3(kBlock), 0, st, p);
-    else hipLaunchKernelGGL((gemm_f16x2_tn_kernel<false, 4>), grid, dim3(kBlock), 0, st, p);
-  }
+  if (KA > 128) launch_f16x2_tn<8>(p, grid, st, full, px);           // [r4] X up to 256 columns wide: eight waves on one staged G tile
+  else launch_f16x2_tn<4>(p, grid, st, full, px);
   p.want_bad = 1;                                                    // the six-product form takes over when the scale kernels said so
   for (int j = 0; j < KA; j += 128) {                                // (it holds 128 columns of X per launch: the same partial tiles)
     TnParams q = p;
     q.X = X + j; q.KA = KA - j < 128 ? KA - j : 128;
     q.part = p.part + (size_t)j * NC; q.part_ss = (int64_t)KA * NC;
-    const bool fq = NC % 128 == 0 && q.KA % 32 == 0;
-    if (fq) hipLaunchKernelGGL(gemm_x3_tn_kernel<true>, grid, dim3(kBlock), 0, st, q);
-    else hipLaunchKernelGGL(gemm_x3_tn_kernel<false>, grid, dim3(kBlock), 0, st, q);
+    launch_x3_tn(q, grid, st);
   }
   if (int rc = check_launch("gemm_f16x2_tn_kernel")) return rc;
   if (s == 1) return 0;
