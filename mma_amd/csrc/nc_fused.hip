@@ -9,7 +9,7 @@
 // 64 at a time (one coalesced load) and handed to the sub-rows with ds_bpermute.  Two edge steps are
 // kept in flight per lane.  Sub-row partial sums meet in a butterfly at the end of the segment; there
 // are no atomics anywhere, so results are bitwise reproducible.
-#include <cstdlib>
+#include <type_traits>
 #include "common.h"
 
 #ifndef NC_FWD_UNROLL
@@ -48,6 +48,12 @@ __device__ __forceinline__ size_t row_off(int row, int64_t ld) { return (size_t)
 
 __device__ __forceinline__ int kind_of(uint32_t kinds, int k) { return (kinds >> (4 * k)) & 0xF; }
 __device__ __forceinline__ uint32_t sel_slot_of(uint32_t slots, int k) { return (slots >> (4 * k)) & 0xFu; }
+// the VEC code bytes of mask k at column c of a packed code row (NcFwdParams::crow); `dflt` for a mask without a slot (sum / mean)
+template <int VEC>
+__device__ __forceinline__ uint32_t crow_codes(const float* crow_row, uint32_t sel_slots, int k, int HQ, int c, uint32_t dflt) {
+  const uint32_t sslot = sel_slot_of(sel_slots, k);
+  return sslot != 0xFu ? ldb<VEC>(reinterpret_cast<const uint8_t*>(crow_row + 4 + (size_t)sslot * HQ) + c) : dflt;
+}
 
 // combine + selection code for one element (layers.py:221,326-329,452,562,676-682,716-720)
 __device__ __forceinline__ float nc_combine(int kind, float xi, float s, float deg, uint32_t& code) {
@@ -408,8 +414,7 @@ __global__ __launch_bounds__(kBlock) void nc_bwd_node_kernel(const NcBwdNodePara
         if (k == 0 || !shared_g) gk[k] = ldv_nt<VEC>(p.g + (size_t)k * p.g_kstride + (size_t)node * p.ldgr + c);
         tk[k] = ldv_nt<VEC>(p.T + o);
         if (p.crow) {
-          ck[k] = sel_slot_of(p.sel_slots, k) != 0xFu
-              ? ldb<VEC>(reinterpret_cast<const uint8_t*>(p.crow + (size_t)node * p.ldc + 4 + (size_t)sel_slot_of(p.sel_slots, k) * p.HQ) + c) : 0u;
+          ck[k] = crow_codes<VEC>(p.crow + (size_t)node * p.ldc, p.sel_slots, k, p.HQ, c, 0u);
         } else {
           ck[k] = ldb_nt<VEC>(p.sel + o);
         }
@@ -489,8 +494,7 @@ __device__ __forceinline__ Vec<VEC> nc_bwd_epilogue(const NcBwdParams& p, int no
   for (int k = 0; k < MMA_MAX_K; ++k) {
     if (k < nk) {
       tk[k] = ldv_nt<VEC>(p.T + row_off(node, p.ldt) + (size_t)(k0 + k) * p.H + c);
-      const uint32_t sslot = sel_slot_of(p.sel_slots, k0 + k);
-      ck[k] = sslot != 0xFu ? ldb<VEC>(reinterpret_cast<const uint8_t*>(crow + 4 + (size_t)sslot * p.HQ) + c) : 0u;
+      ck[k] = crow_codes<VEC>(crow, p.sel_slots, k0 + k, p.HQ, c, 0u);
     }
   }
 #pragma unroll
@@ -515,6 +519,8 @@ __device__ __forceinline__ Vec<VEC> nc_bwd_epilogue(const NcBwdParams& p, int no
 template <int VEC>
 __device__ __forceinline__ void nc_bwd_finalize_body(const NcBwdParams& p, const int4* hubs, int64_t n_hubs, const int64_t first, const int64_t step);
 
+// The lane geometry, the item decode, the keep-factor ladder, the activation pair and the ticket are the same text as in nc_fwd_body,
+// written out in both: as shared functions each of them moved instructions in some kernel ("Shared parts of nc_fused.hip")
 template <int K, int VEC, int DM, bool SHARED, bool MULTI, bool EPI, bool ONE = false>
 __device__ __forceinline__ void nc_bwd_body(const NcBwdParams& p, const int bx, const int nbx) {
   constexpr bool DROP = DM != MMA_DROP_NONE;
@@ -600,9 +606,7 @@ __device__ __forceinline__ void nc_bwd_body(const NcBwdParams& p, const int bx, 
             for (int k = 0; k < K; ++k) {
               // sum/mean never look at the code: a constant "s selected" (2 = twice the factor 1.0) keeps the arithmetic
               // below branch-free
-              const uint32_t sslot = sel_slot_of(p.sel_slots, p.k_base + k);
-              codes[u][k] = (sslot != 0xFu) ? ldb<VEC>(reinterpret_cast<const uint8_t*>(crow + 4 + (size_t)sslot * p.HQ) + cc)
-                                             : 0x02020202u;
+              codes[u][k] = crow_codes<VEC>(crow, p.sel_slots, p.k_base + k, p.HQ, cc, 0x02020202u);
             }
           }
           const float* prow = p.P + row_off(ii, p.ldp) + cc;
@@ -801,6 +805,7 @@ __device__ __forceinline__ void nc_bwd_finalize_body(const NcBwdParams& p, const
         const float* crow = p.crow + row_off(node, p.ldc);
         const float inv_deg = crow[0];
         for (int kk = 0; kk < p.K_total; ++kk) {
+          // written out (not crow_codes): the helper moves instructions in nc_bwd_finalize_kernel<1>
           const uint32_t sslot = sel_slot_of(p.sel_slots, kk);
           const uint32_t ck = sslot != 0xFu ? ldb<VEC>(reinterpret_cast<const uint8_t*>(crow + 4 + (size_t)sslot * p.HQ) + c) : 0u;
 #pragma unroll
@@ -899,65 +904,55 @@ static dim3 item_grid(int64_t n_items, int chunks, int items_per_wave = 1) {
   return dim3((unsigned)blocks, (unsigned)chunks, 1);
 }
 
-template <int K, int VEC, bool MULTI>
-static void launch_fwd(const NcFwdParams& p, dim3 grid, bool save, int dm, hipStream_t st) {
-#define MMA_FWD(SAVE, DM) hipLaunchKernelGGL((nc_fwd_kernel<K, VEC, SAVE, DM, MULTI>), grid, dim3(kBlock), 0, st, p)
-  if (save) {
-    if (dm == MMA_DROP_HASH) MMA_FWD(true, MMA_DROP_HASH); else if (dm == MMA_DROP_HASH16) MMA_FWD(true, MMA_DROP_HASH16); else if (dm == MMA_DROP_EXPLICIT) MMA_FWD(true, MMA_DROP_EXPLICIT); else MMA_FWD(true, MMA_DROP_NONE);
-  } else {
-    if (dm == MMA_DROP_HASH) MMA_FWD(false, MMA_DROP_HASH); else if (dm == MMA_DROP_HASH16) MMA_FWD(false, MMA_DROP_HASH16); else if (dm == MMA_DROP_EXPLICIT) MMA_FWD(false, MMA_DROP_EXPLICIT); else MMA_FWD(false, MMA_DROP_NONE);
+// run-time value -> template argument: f receives it as a std::integral_constant (a generic lambda reads decltype(v)::value).
+// Only what the kernels are instantiated for is reachable: K-slices {1,2,3,4,8}; the one-launch kernels do not exist for
+// explicit masks (EXPLICIT_OK = false: small_plan refuses them); nc_bwd_kernel has no <SHARED = false, EPI = true> (launch_bwd).
+template <int V> using ic = std::integral_constant<int, V>;
+template <class F> static void with_flag(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static void with_k(int Ks, F&& f) {
+  switch (Ks) {
+    case 1: f(ic<1>{}); break;
+    case 2: f(ic<2>{}); break;
+    case 3: f(ic<3>{}); break;
+    case 4: f(ic<4>{}); break;
+    default: f(ic<8>{}); break;
   }
-#undef MMA_FWD
+}
+template <bool EXPLICIT_OK = true, class F> static void with_dm(int dm, F&& f) {
+  if (dm == MMA_DROP_HASH) f(ic<MMA_DROP_HASH>{});
+  else if (dm == MMA_DROP_HASH16) f(ic<MMA_DROP_HASH16>{});
+  else if (EXPLICIT_OK && dm == MMA_DROP_EXPLICIT) f(ic<EXPLICIT_OK ? MMA_DROP_EXPLICIT : MMA_DROP_NONE>{});
+  else f(ic<MMA_DROP_NONE>{});
+}
+// VEC (4 or 1) and MULTI (item part 1: the grouped items) of the item kernels
+template <class F> static void with_form(int vec, int part, F&& f) {
+  with_flag(vec == 4, [&](auto v4) { with_flag(part != 0, [&](auto multi) { f(ic<decltype(v4)::value ? 4 : 1>{}, multi); }); });
+}
+
+template <int VEC, bool MULTI>
+static void launch_fwd(int Ks, const NcFwdParams& p, dim3 grid, bool save, int dm, hipStream_t st) {
+  with_k(Ks, [&](auto k) { with_flag(save, [&](auto sv) { with_dm(dm, [&](auto d) {
+    hipLaunchKernelGGL((nc_fwd_kernel<decltype(k)::value, VEC, decltype(sv)::value, decltype(d)::value, MULTI>), grid, dim3(kBlock), 0, st, p);
+  }); }); });
 }
 template <int VEC, bool MULTI>
-static void launch_fwd_k(int Ks, const NcFwdParams& p, dim3 grid, bool save, int dm, hipStream_t st) {
-  switch (Ks) {
-    case 1: launch_fwd<1, VEC, MULTI>(p, grid, save, dm, st); break;
-    case 2: launch_fwd<2, VEC, MULTI>(p, grid, save, dm, st); break;
-    case 3: launch_fwd<3, VEC, MULTI>(p, grid, save, dm, st); break;
-    case 4: launch_fwd<4, VEC, MULTI>(p, grid, save, dm, st); break;
-    default: launch_fwd<8, VEC, MULTI>(p, grid, save, dm, st); break;
-  }
-}
-template <int K, int VEC, bool MULTI>
-static void launch_bwd(const NcBwdParams& p, dim3 grid, int dm, hipStream_t st) {
-  const bool shared = p.gs == nullptr;
-  const bool epi = p.T != nullptr;
-#define MMA_BWD(DM, SHARED, EPI) hipLaunchKernelGGL((nc_bwd_kernel<K, VEC, DM, SHARED, MULTI, EPI>), grid, dim3(kBlock), 0, st, p)
-#define MMA_BWD_DM(SHARED, EPI) \
-  do { if (dm == MMA_DROP_HASH) MMA_BWD(MMA_DROP_HASH, SHARED, EPI); else if (dm == MMA_DROP_HASH16) MMA_BWD(MMA_DROP_HASH16, SHARED, EPI); else if (dm == MMA_DROP_EXPLICIT) MMA_BWD(MMA_DROP_EXPLICIT, SHARED, EPI); \
-       else MMA_BWD(MMA_DROP_NONE, SHARED, EPI); } while (0)
-  if (shared) { if (epi) MMA_BWD_DM(true, true); else MMA_BWD_DM(true, false); }
-  else MMA_BWD_DM(false, false);
-#undef MMA_BWD_DM
-#undef MMA_BWD
-}
-template <int VEC, bool MULTI>
-static void launch_bwd_k(int Ks, const NcBwdParams& p, dim3 grid, int dm, hipStream_t st) {
-  switch (Ks) {
-    case 1: launch_bwd<1, VEC, MULTI>(p, grid, dm, st); break;
-    case 2: launch_bwd<2, VEC, MULTI>(p, grid, dm, st); break;
-    case 3: launch_bwd<3, VEC, MULTI>(p, grid, dm, st); break;
-    case 4: launch_bwd<4, VEC, MULTI>(p, grid, dm, st); break;
-    default: launch_bwd<8, VEC, MULTI>(p, grid, dm, st); break;
-  }
+static void launch_bwd(int Ks, const NcBwdParams& p, dim3 grid, int dm, hipStream_t st) {
+  with_k(Ks, [&](auto k) { with_dm(dm, [&](auto d) { with_flag(p.gs == nullptr, [&](auto shared) { with_flag(p.T != nullptr, [&](auto epi) {
+    constexpr bool SHARED = decltype(shared)::value, EPI = SHARED && decltype(epi)::value;      // the epilogue exists in the shared form only
+    hipLaunchKernelGGL((nc_bwd_kernel<decltype(k)::value, VEC, decltype(d)::value, SHARED, MULTI, EPI>), grid, dim3(kBlock), 0, st, p);
+  }); }); }); });
 }
 
 // the one-launch form (VEC = 4, hash / no dropout, one K-slice)
-template <int K>
-static void launch_fwd_small(const NcFwdParams& p, const NcSmallPlan& sp, dim3 grid, bool save, int dm, hipStream_t st) {
-#define MMA_FWD_S(SAVE, DM) hipLaunchKernelGGL((nc_fwd_small_kernel<K, 4, SAVE, DM>), grid, dim3(kBlock), 0, st, p, sp)
-  if (save) { if (dm == MMA_DROP_HASH) MMA_FWD_S(true, MMA_DROP_HASH); else if (dm == MMA_DROP_HASH16) MMA_FWD_S(true, MMA_DROP_HASH16); else MMA_FWD_S(true, MMA_DROP_NONE); }
-  else { if (dm == MMA_DROP_HASH) MMA_FWD_S(false, MMA_DROP_HASH); else if (dm == MMA_DROP_HASH16) MMA_FWD_S(false, MMA_DROP_HASH16); else MMA_FWD_S(false, MMA_DROP_NONE); }
-#undef MMA_FWD_S
+static void launch_fwd_small(int K, const NcFwdParams& p, const NcSmallPlan& sp, dim3 grid, bool save, int dm, hipStream_t st) {
+  with_k(K, [&](auto k) { with_flag(save, [&](auto sv) { with_dm<false>(dm, [&](auto d) {
+    hipLaunchKernelGGL((nc_fwd_small_kernel<decltype(k)::value, 4, decltype(sv)::value, decltype(d)::value>), grid, dim3(kBlock), 0, st, p, sp);
+  }); }); });
 }
-template <int K>
-static void launch_bwd_small(const NcBwdParams& p, const NcSmallPlan& sp, dim3 grid, int dm, hipStream_t st) {
-  const bool epi = p.T != nullptr;
-#define MMA_BWD_S(DM, EPI) hipLaunchKernelGGL((nc_bwd_small_kernel<K, 4, DM, EPI>), grid, dim3(kBlock), 0, st, p, sp)
-  if (epi) { if (dm == MMA_DROP_HASH) MMA_BWD_S(MMA_DROP_HASH, true); else if (dm == MMA_DROP_HASH16) MMA_BWD_S(MMA_DROP_HASH16, true); else MMA_BWD_S(MMA_DROP_NONE, true); }
-  else { if (dm == MMA_DROP_HASH) MMA_BWD_S(MMA_DROP_HASH, false); else if (dm == MMA_DROP_HASH16) MMA_BWD_S(MMA_DROP_HASH16, false); else MMA_BWD_S(MMA_DROP_NONE, false); }
-#undef MMA_BWD_S
+static void launch_bwd_small(int K, const NcBwdParams& p, const NcSmallPlan& sp, dim3 grid, int dm, hipStream_t st) {
+  with_k(K, [&](auto k) { with_flag(p.T != nullptr, [&](auto epi) { with_dm<false>(dm, [&](auto d) {
+    hipLaunchKernelGGL((nc_bwd_small_kernel<decltype(k)::value, 4, decltype(d)::value, decltype(epi)::value>), grid, dim3(kBlock), 0, st, p, sp);
+  }); }); });
 }
 // Is the one-launch form possible?  Fills the plan (grid = blocks_a + blocks_b) when it is.  The hub sums are done by ONE wavefront
 // (the one that stores the last chunk partial), so they must be few: `finalize_elems` = (hubs) x (vectors per row) [x (K+1)].
@@ -983,6 +978,51 @@ static int64_t elementwise_grid(int64_t total) {
   return b < 1 ? 1 : (b > kMaxGrid * 4 ? kMaxGrid * 4 : b);
 }
 
+// ---- what mma_nc_fused_fwd and mma_nc_fused_bwd share.  The three check helpers are the shared requirements in the order the entry
+// points have always made them: each entry point's own checks sit between them.
+static int nc_common_checks(int64_t N, int64_t E, int32_t H, int32_t K) {
+  MMA_REQUIRE(N >= 0 && E >= 0 && N < (1LL << 31) && E < (1LL << 31), "N=%lld E=%lld out of int32 range", (long long)N, (long long)E);
+  MMA_REQUIRE(H >= 1 && K >= 1 && K <= MMA_MAX_K, "H=%d K=%d unsupported (1<=K<=%d)", H, K, MMA_MAX_K);
+  return 0;
+}
+static int nc_item_checks(int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs, const float* partial, int64_t n_slots) {
+  MMA_REQUIRE(n_items >= 0 && n_hubs >= 0 && n_slots >= 0 && n_items < (1LL << 31) && n_wave_items >= 0, "negative or oversize item counts");
+  MMA_REQUIRE(n_slots == 0 || (partial != nullptr && hubs != nullptr && n_hubs > 0), "hub slots without partial/hubs buffers");
+  return 0;
+}
+static int nc_item_alignment(const int32_t* items, const int32_t* hubs) {
+  MMA_REQUIRE(aligned16(items) && (hubs == nullptr || aligned16(hubs)), "items/hubs must be 16-byte aligned int32 quadruples");
+  return 0;
+}
+// items [0, n_wave_items): one per wavefront; items [n_wave_items, n_items): one per LPR-lane group (short segments)
+static int64_t nc_wave_items(int ipw, int64_t n_items, int64_t n_wave_items) {
+  return (ipw == 1 || n_wave_items > n_items) ? n_items : n_wave_items;
+}
+// the hub list and the ticket counter of the one-launch form
+template <class Params>
+static void nc_set_hubs(Params& p, const int32_t* hubs, int64_t n_hubs, int32_t* sync, int64_t n_slots) {
+  p.hubs = reinterpret_cast<const int4*>(hubs); p.n_hubs = n_hubs; p.sync = reinterpret_cast<unsigned*>(sync); p.n_slots = (unsigned)n_slots;
+}
+// the separate launches: (wave items, grouped items) x K-slices.  Sets p.items / p.n_items / p.k_base, then f(part, k0, ks, grid).
+template <class Params, class F>
+static void nc_for_slices(Params& p, int64_t n_wave_items, int K, const Geometry& g, F&& f) {
+  const int4* all_items = p.items;
+  const int64_t n_items = p.n_items;
+  for (int part = 0; part < 2; ++part) {
+    const int64_t cnt = part == 0 ? n_wave_items : n_items - n_wave_items;
+    if (cnt <= 0) continue;
+    p.items = all_items + (part == 0 ? 0 : n_wave_items);
+    p.n_items = cnt;
+    const dim3 grid = item_grid(cnt, g.chunks, part == 0 ? 1 : (kWave >> g.lpr_log));
+    for (int k0 = 0; k0 < K;) {
+      const int ks = next_slice(K - k0);
+      p.k_base = k0;
+      f(part, k0, ks, grid);
+      k0 += ks;
+    }
+  }
+}
+
 }  // namespace mma
 
 using namespace mma;
@@ -996,22 +1036,20 @@ extern "C" int mma_nc_fused_fwd(
     int64_t N, int64_t E, int32_t H, int32_t K, const uint8_t* kind_host, const uint8_t* act_host,
     int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
     int32_t* sync, void* stream) {
-  MMA_REQUIRE(N >= 0 && E >= 0 && N < (1LL << 31) && E < (1LL << 31), "N=%lld E=%lld out of int32 range", (long long)N, (long long)E);
-  MMA_REQUIRE(H >= 1 && K >= 1 && K <= MMA_MAX_K, "H=%d K=%d unsupported (1<=K<=%d)", H, K, MMA_MAX_K);
+  if (int rc = nc_common_checks(N, E, H, K)) return rc;
   MMA_REQUIRE(ldx >= H && ldp >= (int64_t)K * H && ldq >= (int64_t)K * H, "row pitch too small: ldx=%lld ldp=%lld ldq=%lld",
               (long long)ldx, (long long)ldp, (long long)ldq);
   MMA_REQUIRE(T != nullptr || (sel == nullptr && crow == nullptr), "sel / crow are saved next to T: give T too");
   MMA_REQUIRE(T == nullptr || sel != nullptr || crow != nullptr, "T needs the selection state beside it: sel (N,K*H), crow (N,ldc), or both");
   MMA_REQUIRE(T == nullptr || ldt >= (int64_t)K * H, "ldt=%lld too small", (long long)ldt);
   MMA_REQUIRE(ldx < (1LL << 31) && ldp < (1LL << 31) && ldq < (1LL << 31) && ldt < (1LL << 31) && ldc < (1LL << 31), "row pitch out of range");
-  MMA_REQUIRE(n_items >= 0 && n_hubs >= 0 && n_slots >= 0 && n_items < (1LL << 31) && n_wave_items >= 0, "negative or oversize item counts");
-  MMA_REQUIRE(n_slots == 0 || (partial != nullptr && hubs != nullptr && n_hubs > 0), "hub slots without partial/hubs buffers");
+  if (int rc = nc_item_checks(n_items, n_wave_items, hubs, n_hubs, partial, n_slots)) return rc;
   if (N == 0 || n_items == 0) return 0;
   MMA_REQUIRE(x && P && Q && rowptr && items && kind_host && act_host, "NULL argument");
   MMA_REQUIRE(m != nullptr || m_sum != nullptr, "give m (K,N,H), m_sum (N,H), or both");
   MMA_REQUIRE(m_sum == nullptr || ldms >= H, "ldms=%lld too small", (long long)ldms);
   MMA_REQUIRE(E == 0 || col != nullptr, "NULL col");
-  MMA_REQUIRE(aligned16(items) && (hubs == nullptr || aligned16(hubs)), "items/hubs must be 16-byte aligned int32 quadruples");
+  if (int rc = nc_item_alignment(items, hubs)) return rc;
   uint32_t kinds, acts;
   if (int rc = pack_codes(kind_host, act_host, K, &kinds, &acts)) return rc;
   NcFwdParams p{};
@@ -1028,61 +1066,33 @@ extern "C" int mma_nc_fused_fwd(
                   (!save || (aligned16(T) && (!sel || aligned16(sel)))) && (partial == nullptr || aligned16(partial));
   const Geometry g = geometry(H, v4);
   p.x = x; p.ldx = ldx; p.P = P; p.ldp = ldp; p.Q = Q; p.ldq = ldq; p.rowptr = rowptr; p.col = col;
-  // MEASUREMENT ONLY (round-3 VERDICT item 6, "P inside K1": what would K1 gain if it did not have to read P?): MMA_NC_ABLATE_P=1 makes
-  // every target read P's row 0 (a cache hit) - the results are WRONG, only the kernel's time means anything.  DESIGN.md 9 has the number.
-  static const bool ablate_p = getenv("MMA_NC_ABLATE_P") && atoi(getenv("MMA_NC_ABLATE_P")) != 0;
-  if (ablate_p) p.ldp = 0;
   p.items = reinterpret_cast<const int4*>(items); p.n_items = n_items;
   p.partial = partial; p.pstride = 2LL * K * H;
   p.m = m; p.m_kstride = N * (int64_t)H; p.msum = m_sum; p.ldms = ldms; p.T = T; p.sel = sel; p.ldt = ldt;
   p.crow = crow; p.ldc = ldc;
   p.H = H; p.HQ = (H + 3) / 4; p.K_total = K; p.lpr_log = g.lpr_log; p.kinds = kinds; p.acts = acts;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  // items [0, n_wave_items): one per wavefront; items [n_wave_items, n_items): one per LPR-lane group (short segments)
-  const int ipw = kWave >> g.lpr_log;
-  if (ipw == 1 || n_wave_items > n_items) n_wave_items = n_items;
-  const int4* all_items = p.items;
+  n_wave_items = nc_wave_items(kWave >> g.lpr_log, n_items, n_wave_items);
   {
     NcSmallPlan sp; dim3 sgrid;
     if (small_plan(sync, K, g, dm, n_items, n_wave_items, n_hubs, n_slots, n_hubs * ((H + 3) / 4), &sp, &sgrid)) {
       p.k_base = 0;
-      p.hubs = reinterpret_cast<const int4*>(hubs); p.n_hubs = n_hubs; p.sync = reinterpret_cast<unsigned*>(sync); p.n_slots = (unsigned)n_slots;
-      switch (K) {
-        case 1: launch_fwd_small<1>(p, sp, sgrid, save, dm, st); break;
-        case 2: launch_fwd_small<2>(p, sp, sgrid, save, dm, st); break;
-        case 3: launch_fwd_small<3>(p, sp, sgrid, save, dm, st); break;
-        case 4: launch_fwd_small<4>(p, sp, sgrid, save, dm, st); break;
-        default: launch_fwd_small<8>(p, sp, sgrid, save, dm, st); break;
-      }
+      nc_set_hubs(p, hubs, n_hubs, sync, n_slots);
+      launch_fwd_small(K, p, sp, sgrid, save, dm, st);
       return check_launch("nc_fwd_small_kernel");
     }
   }
-  for (int part = 0; part < 2; ++part) {
-    const int64_t cnt = part == 0 ? n_wave_items : n_items - n_wave_items;
-    if (cnt <= 0) continue;
-    p.items = all_items + (part == 0 ? 0 : n_wave_items);
-    p.n_items = cnt;
-    const dim3 grid = item_grid(cnt, g.chunks, part == 0 ? 1 : ipw);
-    for (int k0 = 0; k0 < K;) {
-      const int ks = next_slice(K - k0);
-      p.k_base = k0;
-      if (g.vec == 4) { if (part == 0) launch_fwd_k<4, false>(ks, p, grid, save, dm, st); else launch_fwd_k<4, true>(ks, p, grid, save, dm, st); }
-      else { if (part == 0) launch_fwd_k<1, false>(ks, p, grid, save, dm, st); else launch_fwd_k<1, true>(ks, p, grid, save, dm, st); }
-      k0 += ks;
-    }
-  }
+  nc_for_slices(p, n_wave_items, K, g, [&](int part, int, int ks, dim3 grid) {
+    with_form(g.vec, part, [&](auto vec, auto multi) { launch_fwd<decltype(vec)::value, decltype(multi)::value>(ks, p, grid, save, dm, st); });
+  });
   if (int rc = check_launch("nc_fwd_kernel")) return rc;
   if (n_hubs > 0) {
     const int per_row = (H + g.vec - 1) / g.vec;
     const dim3 fg((unsigned)elementwise_grid(n_hubs * per_row));
     const int4* hb = reinterpret_cast<const int4*>(hubs);
-    if (g.vec == 4) {
-      if (save) hipLaunchKernelGGL((nc_fwd_finalize_kernel<4, true>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
-      else hipLaunchKernelGGL((nc_fwd_finalize_kernel<4, false>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
-    } else {
-      if (save) hipLaunchKernelGGL((nc_fwd_finalize_kernel<1, true>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
-      else hipLaunchKernelGGL((nc_fwd_finalize_kernel<1, false>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
-    }
+    with_flag(g.vec == 4, [&](auto v4) { with_flag(save, [&](auto sv) {
+      hipLaunchKernelGGL((nc_fwd_finalize_kernel<decltype(v4)::value ? 4 : 1, decltype(sv)::value>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
+    }); });
     if (int rc = check_launch("nc_fwd_finalize_kernel")) return rc;
   }
   return 0;
@@ -1135,14 +1145,12 @@ extern "C" int mma_nc_fused_bwd(
     int64_t N, int64_t E, int32_t H, int32_t K, const uint8_t* act_host,
     int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
     int32_t* sync, void* stream) {
-  MMA_REQUIRE(N >= 0 && E >= 0 && N < (1LL << 31) && E < (1LL << 31), "N=%lld E=%lld out of int32 range", (long long)N, (long long)E);
-  MMA_REQUIRE(H >= 1 && K >= 1 && K <= MMA_MAX_K, "H=%d K=%d unsupported (1<=K<=%d)", H, K, MMA_MAX_K);
+  if (int rc = nc_common_checks(N, E, H, K)) return rc;
   MMA_REQUIRE(ldx >= H && ldp >= (int64_t)K * H && ldq >= (int64_t)K * H && (!gs || ldg >= (int64_t)K * H) && ldgq >= (int64_t)K * H &&
               ldgxo >= H, "row pitch too small");
   MMA_REQUIRE(ldx < (1LL << 31) && ldp < (1LL << 31) && ldq < (1LL << 31) && ldg < (1LL << 31) && ldgg < (1LL << 31) && ldc < (1LL << 31) &&
               ldt < (1LL << 31) && ldgp < (1LL << 31) && ldgq < (1LL << 31) && ldgx < (1LL << 31) && ldgxo < (1LL << 31), "row pitch out of range");
-  MMA_REQUIRE(n_items >= 0 && n_hubs >= 0 && n_slots >= 0 && n_items < (1LL << 31) && n_wave_items >= 0, "negative or oversize item counts");
-  MMA_REQUIRE(n_slots == 0 || (partial != nullptr && hubs != nullptr && n_hubs > 0), "hub slots without partial/hubs buffers");
+  if (int rc = nc_item_checks(n_items, n_wave_items, hubs, n_hubs, partial, n_slots)) return rc;
   if (N == 0 || n_items == 0) return 0;       // an empty shard: nothing to do (its zero-row buffers are NULL)
   const bool shared = gs == nullptr;
   const bool epi = T != nullptr;
@@ -1153,7 +1161,7 @@ extern "C" int mma_nc_fused_bwd(
   MMA_REQUIRE(epi || (gxs && ldgx >= H), "gxs (N,H) from mma_nc_bwd_node is needed unless the epilogue is fused (T given)");
   MMA_REQUIRE(x && P && Q && items && gQ && gx && act_host, "NULL argument");
   MMA_REQUIRE(E == 0 || (t_col != nullptr && t_eid != nullptr), "NULL transposed CSR");
-  MMA_REQUIRE(aligned16(items) && (hubs == nullptr || aligned16(hubs)), "items/hubs must be 16-byte aligned int32 quadruples");
+  if (int rc = nc_item_alignment(items, hubs)) return rc;
   uint32_t kinds, acts;
   if (int rc = pack_codes(shared ? kind_host : nullptr, act_host, K, &kinds, &acts)) return rc;
   NcBwdParams p{};
@@ -1177,45 +1185,28 @@ extern "C" int mma_nc_fused_bwd(
   p.rowmax = reinterpret_cast<uint32_t*>(row_max);
   p.H = H; p.HQ = (H + 3) / 4; p.K_total = K; p.lpr_log = geo.lpr_log; p.acts = acts;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int ipw = kWave >> geo.lpr_log;
-  if (ipw == 1 || n_wave_items > n_items) n_wave_items = n_items;
-  const int4* all_items = p.items;
+  n_wave_items = nc_wave_items(kWave >> geo.lpr_log, n_items, n_wave_items);
   {
     NcSmallPlan sp; dim3 sgrid;
     if (shared && small_plan(sync, K, geo, dm, n_items, n_wave_items, n_hubs, n_slots, n_hubs * (K + 1) * ((H + 3) / 4), &sp, &sgrid)) {
       p.k_base = 0; p.first_pass = 1;
-      p.hubs = reinterpret_cast<const int4*>(hubs); p.n_hubs = n_hubs; p.sync = reinterpret_cast<unsigned*>(sync); p.n_slots = (unsigned)n_slots;
-      switch (K) {
-        case 1: launch_bwd_small<1>(p, sp, sgrid, dm, st); break;
-        case 2: launch_bwd_small<2>(p, sp, sgrid, dm, st); break;
-        case 3: launch_bwd_small<3>(p, sp, sgrid, dm, st); break;
-        case 4: launch_bwd_small<4>(p, sp, sgrid, dm, st); break;
-        default: launch_bwd_small<8>(p, sp, sgrid, dm, st); break;
-      }
+      nc_set_hubs(p, hubs, n_hubs, sync, n_slots);
+      launch_bwd_small(K, p, sp, sgrid, dm, st);
       return check_launch("nc_bwd_small_kernel");
     }
   }
-  for (int part = 0; part < 2; ++part) {
-    const int64_t cnt = part == 0 ? n_wave_items : n_items - n_wave_items;
-    if (cnt <= 0) continue;
-    p.items = all_items + (part == 0 ? 0 : n_wave_items);
-    p.n_items = cnt;
-    const dim3 grid = item_grid(cnt, geo.chunks, part == 0 ? 1 : ipw);
-    for (int k0 = 0; k0 < K;) {
-      const int ks = next_slice(K - k0);
-      p.k_base = k0; p.first_pass = (k0 == 0);
-      if (geo.vec == 4) { if (part == 0) launch_bwd_k<4, false>(ks, p, grid, dm, st); else launch_bwd_k<4, true>(ks, p, grid, dm, st); }
-      else { if (part == 0) launch_bwd_k<1, false>(ks, p, grid, dm, st); else launch_bwd_k<1, true>(ks, p, grid, dm, st); }
-      k0 += ks;
-    }
-  }
+  nc_for_slices(p, n_wave_items, K, geo, [&](int part, int k0, int ks, dim3 grid) {
+    p.first_pass = (k0 == 0);
+    with_form(geo.vec, part, [&](auto vec, auto multi) { launch_bwd<decltype(vec)::value, decltype(multi)::value>(ks, p, grid, dm, st); });
+  });
   if (int rc = check_launch("nc_bwd_kernel")) return rc;
   if (n_hubs > 0) {
     const int per_row = (H + geo.vec - 1) / geo.vec;
     const dim3 fg((unsigned)elementwise_grid(n_hubs * (K + 1) * per_row));
     const int4* hb = reinterpret_cast<const int4*>(hubs);
-    if (geo.vec == 4) hipLaunchKernelGGL((nc_bwd_finalize_kernel<4>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
-    else hipLaunchKernelGGL((nc_bwd_finalize_kernel<1>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
+    with_flag(geo.vec == 4, [&](auto v4) {
+      hipLaunchKernelGGL((nc_bwd_finalize_kernel<decltype(v4)::value ? 4 : 1>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
+    });
     if (int rc = check_launch("nc_bwd_finalize_kernel")) return rc;
   }
   return 0;

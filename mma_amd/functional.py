@@ -150,6 +150,26 @@ def nc_bwd_edges_launch(x_src, P, Q, gs, g, crow, gxs, graph, kinds, acts, drop,
              keep, ptr(graph.sync(1)) if part is None else None, stream_ptr())
 
 
+def nc_bwd_plan(x_src, P, Q, g, T, sel, crow, graph, kinds, acts, drop, reduce_k, gP, gQ, gx, row_max=None):
+    """The NC backward's choreography, once -> (gP, run).  K2a runs in K2b's per-source epilogue when the selection state is the
+    packed code rows `crow` (shared-gradient form) and FUSE_NODE_BWD is on; else it is launched here.  gP (N,K*H) is allocated when
+    the caller gave none.  run(part=None): ONE K2b launch over `part` = (items, n_wave_items, hubs) of the sources (default: all)."""
+    K, H = len(kinds), x_src.shape[1]
+    shared = crow is not None
+    fuse = shared and FUSE_NODE_BWD
+    gs = gxs = None
+    if not fuse:
+        gs, gP, gxs = nc_bwd_node_launch(g, reduce_k, sel, crow, T, graph, kinds, H, shared, gP=gP, row_max=row_max)
+    elif gP is None:
+        gP = torch.empty((graph.N, K * H), device=g.device, dtype=torch.float32)
+    epi = dict(T=T, gP=gP) if fuse else {}
+    partial = torch.empty((graph.t_n_slots, (K + 1) * H), device=g.device, dtype=torch.float32) if graph.t_n_slots else None
+
+    def run(part=None):
+        nc_bwd_edges_launch(x_src, P, Q, gs, g, crow, gxs, graph, kinds, acts, drop, gQ, gx, partial, part, row_max=row_max, **epi)
+    return gP, run
+
+
 class _NCFused(torch.autograd.Function):
     """m[k] = combine_k(x_i, sum_j drop(act_k(P_k[i] + Q_k[j])) * x_j)   (K1 forward, K2a + K2b backward).
     reduce_k: return sum_k m[k] (N,H) instead of (K,N,H) - all MMA.forward needs; backward then takes the
@@ -174,21 +194,12 @@ class _NCFused(torch.autograd.Function):
     def backward(ctx, g):
         graph, kinds, acts, drop, reduce_k = ctx.graph, ctx.kinds, ctx.acts, ctx.drop, ctx.reduce_k
         x_src, P, Q, T, sel, crow = ctx.saved_tensors
-        shared = crow is not None
-        K = len(kinds)
-        H, S = x_src.shape[1], graph.n_src
+        K, H, S = len(kinds), x_src.shape[1], graph.n_src
         g = g.contiguous()
-        dev = g.device
-        gQ = torch.empty((S, K * H), device=dev, dtype=torch.float32)
-        gx = torch.empty((S, H), device=dev, dtype=torch.float32)
-        partial = (torch.empty((graph.t_n_slots, (K + 1) * H), device=dev, dtype=torch.float32)
-                   if graph.t_n_slots else None)
-        if shared and FUSE_NODE_BWD:
-            gP = torch.empty((graph.N, K * H), device=dev, dtype=torch.float32)
-            nc_bwd_edges_launch(x_src, P, Q, None, g, crow, None, graph, kinds, acts, drop, gQ, gx, partial, T=T, gP=gP)
-        else:
-            gs, gP, gxs = nc_bwd_node_launch(g, reduce_k, sel, crow, T, graph, kinds, H, shared)
-            nc_bwd_edges_launch(x_src, P, Q, gs, g, crow, gxs, graph, kinds, acts, drop, gQ, gx, partial)
+        gQ = torch.empty((S, K * H), device=g.device, dtype=torch.float32)
+        gx = torch.empty((S, H), device=g.device, dtype=torch.float32)
+        gP, run = nc_bwd_plan(x_src, P, Q, g, T, sel, crow, graph, kinds, acts, drop, reduce_k, None, gQ, gx)
+        run()
         return gx, gP, gQ, None, None, None, None, None
 
 
@@ -228,16 +239,9 @@ class _NCLocalLayer(torch.autograd.Function):
         # the three-product dL/dx GEMM scales every row of [gP|gQ] by a power of two: K2a and K2b leave the row maxima here
         row_max = torch.zeros((N,), device=g.device, dtype=torch.float32) if f16x2_n128_ok(N, 2 * KH, H) and K <= 8 else None
         gx = torch.empty((N, H), device=g.device, dtype=torch.float32)
-        partial = (torch.empty((graph.t_n_slots, (K + 1) * H), device=g.device, dtype=torch.float32)
-                   if graph.t_n_slots else None)
-        shared = crow is not None
-        if shared and FUSE_NODE_BWD:         # K2a inside K2b's epilogue: gP lands in the left half of [gP | gQ] from the same launch
-            nc_bwd_edges_launch(x, PQ[:, :KH], PQ[:, KH:], None, g, crow, None, graph, kinds, acts, drop, gPQ[:, KH:], gx, partial,
-                                row_max=row_max, T=T, gP=gPQ[:, :KH])
-        else:
-            gs, gP, gxs = nc_bwd_node_launch(g, True, sel, crow, T, graph, kinds, H, shared, gP=gPQ[:, :KH], row_max=row_max)
-            nc_bwd_edges_launch(x, PQ[:, :KH], PQ[:, KH:], gs, g, crow, gxs, graph, kinds, acts, drop, gPQ[:, KH:], gx, partial,
-                                row_max=row_max)
+        # gP lands in the left half of [gP | gQ], from K2a or from K2b's epilogue
+        _, run = nc_bwd_plan(x, PQ[:, :KH], PQ[:, KH:], g, T, sel, crow, graph, kinds, acts, drop, True, gPQ[:, :KH], gPQ[:, KH:], gx, row_max)
+        run()
         rows_mm_add_(gx, gPQ, wcat.t(), row_max)                             # direct + through P and Q in one GEMM (C += A B)
         gw = xt_g(x, gPQ, x_row_max, row_max) if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) else None
         if ctx.cat_given:

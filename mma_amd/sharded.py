@@ -434,33 +434,28 @@ class _ShardedAggregate(torch.autograd.Function):
         KH = K * H
         dev = g.device
         g = g.contiguous()
-        shared = crow is not None
-        fuse = shared and Fn.FUSE_NODE_BWD          # K2a in the epilogue of the OWN-source launch (halo sources have no target role)
         gP = torch.empty((n, KH), device=dev, dtype=torch.float32)
         gQ = torch.empty((S, KH), device=dev, dtype=torch.float32)
         from .dense import f16x2_n128_ok, rows_mm_add_
         # row maxima of gP / gQ for the three-product dL/dx GEMMs (own rows: the larger of both; halo rows: gQ only)
         row_max = torch.zeros((S,), device=dev, dtype=torch.float32) if f16x2_n128_ok(max(n, S - n), KH, H) and K <= 8 else None
-        gs = gxs = None
-        if not fuse:
-            gs, _gP, gxs = Fn.nc_bwd_node_launch(g, True, sel, crow, T, graph, kinds, H, shared, gP=gP, row_max=row_max)
-        epi = dict(T=T, gP=gP) if fuse else {}
         gx = torch.empty((S, H), device=dev, dtype=torch.float32)
-        partial = (torch.empty((graph.t_n_slots, (K + 1) * H), device=dev, dtype=torch.float32) if graph.t_n_slots else None)
+        # K2a now, or in the epilogue of the OWN-source launch (halo sources have no target role)
+        _, run = Fn.nc_bwd_plan(x_src, P, Q, g, T, sel, crow, graph, kinds, acts, drop, True, gP, gQ, gx, row_max)
         # The reverse exchange is a COLLECTIVE: every rank of a multi-rank plan joins it, also one that has no halo rows of
         # its own (a directed graph, or an empty shard) - its peers may still owe it gradient rows (send_counts > 0), and a
         # rank that skipped the call would leave them blocked or matched against its next collective.
         back = None
         if S > n:
             halo_part, own_part = graph.t_parts
-            Fn.nc_bwd_edges_launch(x_src, P, Q, gs, g, crow, gxs, graph, kinds, acts, drop, gQ, gx, partial, halo_part, row_max=row_max, **epi)
+            run(halo_part)
             gxh = rows_mm_add_(gx[n:], gQ[n:], wbot.t(), row_max[n:] if row_max is not None else None)   # halo rows: direct + via Q
             back = all_to_all_rows_start(gxh, plan.recv_counts, plan.send_counts, plan.group)
-            Fn.nc_bwd_edges_launch(x_src, P, Q, gs, g, crow, gxs, graph, kinds, acts, drop, gQ, gx, partial, own_part, row_max=row_max, **epi)
+            run(own_part)
         else:
             if plan.world > 1:
                 back = all_to_all_rows_start(gx[n:], plan.recv_counts, plan.send_counts, plan.group)    # sends (0,H), still receives
-            Fn.nc_bwd_edges_launch(x_src, P, Q, gs, g, crow, gxs, graph, kinds, acts, drop, gQ, gx, partial, row_max=row_max, **epi)
+            run()
         rm_own = row_max[:n] if row_max is not None else None
         gx_own = rows_mm_add_(gx[:n], gP, wtop.t(), rm_own)                    # own rows: direct + through P ...
         gx_own = rows_mm_add_(gx_own, gQ[:n], wbot.t(), rm_own)                # ... + through Q
