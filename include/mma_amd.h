@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MMA_ABI_VERSION 36
+#define MMA_ABI_VERSION 37
 #define MMA_MAX_K 8          /* masks fused per launch; more are issued as several launches */
 
 /* combine kinds of the node-classification aggregators (layers.py:201-728) */
@@ -152,6 +152,49 @@ int mma_nc_fused_bwd(
     const uint8_t* act_host,
     int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
     int32_t* sync,                               /* optional, as in mma_nc_fused_fwd (shared-gradient form only): ONE launch */
+    void* stream);
+
+/* ---- K1s / K2s (ABI 37): the second-moment ("std") aggregator of the node-classification layer ------------------------
+ * An extension (MMA(..., strict_reference=False)): the reference's learnable_std (layers.py:731-771) cannot run, this is its evident
+ * intent (DESIGN.md "std aggregator").  ONE mask; per target i with d = max(d_i, 1), per feature column:
+ *     z(i,j)  = P[i] + Q[j]                a = sigmoid(z), or z itself with act_host[0] == MMA_ACT_RAW
+ *     mu(i,j) = drop * a * x_j             mean = (1/d) sum_j mu      msq = (1/d) sum_j mu^2
+ *     m[i]    = sqrt(max(msq - mean^2, 0) + 1e-5)                    (no self term x_i; an isolated node gives sqrt(1e-5))
+ * items / hubs / partial as in mma_nc_fused_fwd (same NCGraph lists, hub chunk partials summed in slot order, no atomics); the
+ * sqrt is taken after the full-segment sums only.  With `saved` (N, 3H) the kernel also leaves what the backward needs,
+ *     saved[i] = [ mean | r = [msq - mean^2 > 0] / (d m) | r (T2 - mean T1) ],   T1 = sum_j drop x_j a',  T2 = sum_j mu drop x_j a',
+ * The sums are held in fp64 (msq - mean^2 and T2 - mean T1 cancel), so `partial` is fp64 scratch: (n_slots, 2, H), or (n_slots, 4, H)
+ * when saving. */
+int mma_nc_std_fwd(
+    const float* x, int64_t ldx,                 /* (n_src,H): rows [0,N) are the targets */
+    const float* P, int64_t ldp,                 /* (N,H)     x @ W[:H] */
+    const float* Q, int64_t ldq,                 /* (n_src,H) x @ W[H:] */
+    const int32_t* rowptr, const int32_t* col,
+    const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
+    double* partial, int64_t n_slots,            /* (n_slots, 2H) fp64 scratch ((n_slots, 4H) when saving), NULL when n_slots == 0 */
+    float* m, int64_t ldms,                      /* (N,H) out */
+    float* saved, int64_t ldt,                   /* (N,3H) out, or NULL: nothing is saved */
+    int64_t N, int64_t E, int32_t H,
+    const uint8_t* act_host,                     /* ONE MMA_ACT_* code, HOST memory */
+    int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base,
+    const uint8_t* keep,                         /* EXPLICIT: (1,E,H), else NULL */
+    void* stream);
+/* Backward of the above from g = dL/dm (n_targets,H).  A node pass forms gP = g * saved[:, 2H:] and gr = g * saved[:, H:2H]
+ * (n_targets,H each); the edge pass walks the TRANSPOSED lists as mma_nc_fused_bwd does and, per edge (i -> source j), gathers the
+ * target's P, gr and mean rows, recomputes a, a' and the dropout factor of the forward (t_eid keys the bits) and sums
+ *     e = gr[i] (mu - mean[i]),   gQ[j] = x_j sum_i e drop a',   gx[j] = sum_i e drop a
+ * in a fixed order (partial: (n_slots, 2, H)).  N is the number of SOURCE rows; sources >= n_targets have no target role. */
+int mma_nc_std_bwd(
+    const float* x, int64_t ldx, const float* P, int64_t ldp, const float* Q, int64_t ldq,
+    const float* g, int64_t ldg, const float* saved, int64_t ldt,
+    float* gr, int64_t ldgr,                     /* (n_targets,H) scratch out */
+    float* gP, int64_t ldgp, int64_t n_targets,
+    const int32_t* t_col, const int32_t* t_eid,
+    const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
+    float* partial, int64_t n_slots,
+    float* gQ, int64_t ldgq, float* gx, int64_t ldgx,
+    int64_t N, int64_t E, int32_t H, const uint8_t* act_host,
+    int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
     void* stream);
 
 /* ---- K5: CSR SpMM over a K-times column-stacked adjacency ----------------------------------------

@@ -322,6 +322,78 @@ def nc_fused_aggregate(x, P, Q, graph, kinds, acts, drop=None, reduce_k=False):
     return _NCFused.apply(x, P, Q, graph, tuple(kinds), tuple(acts), drop or DropoutSpec(0.0), bool(reduce_k))
 
 
+class _NCStd(torch.autograd.Function):
+    """m = sqrt(relu(E_j[mu^2] - E_j[mu]^2) + 1e-5), mu = drop(act(P[i] + Q[j])) * x_j over the neighbours j of target i: the
+    second-moment aggregator (K1s forward, K2s backward; include/mma_amd.h ABI 37, DESIGN.md "std aggregator").  Shaped like
+    _NCFused: inputs x_src, P, Q, backward returns gx, gP, gQ."""
+
+    @staticmethod
+    def forward(ctx, x_src, P, Q, graph, act, drop):
+        require_gpu(x_src, P, Q)
+        x_src = x_src.contiguous()
+        if P.stride(1) != 1:
+            P = P.contiguous()
+        if Q.stride(1) != 1:
+            Q = Q.contiguous()
+        S, H = x_src.shape
+        N, E = graph.N, graph.E
+        assert x_src.dtype == torch.float32 and P.dtype == torch.float32 and Q.dtype == torch.float32
+        assert S == graph.n_src and P.shape == (N, H) and Q.shape == (S, H)
+        dev = x_src.device
+        save = any(ctx.needs_input_grad[:3])
+        m = torch.empty((N, H), device=dev, dtype=torch.float32)
+        saved = torch.empty((N, 3 * H), device=dev, dtype=torch.float32) if save else None        # [mean | r | r (T2 - mean T1)]
+        # hub chunk partials: the two (saving: four) sums per column, held in fp64
+        partial = torch.empty((graph.n_slots, (4 if save else 2) * H), device=dev, dtype=torch.float64) if graph.n_slots else None
+        if drop.keep is not None:
+            assert drop.keep.dtype == torch.uint8 and drop.keep.is_contiguous() and drop.keep.is_cuda and \
+                tuple(drop.keep.shape) == (1, E, H), "explicit keep mask must be a contiguous (1,E,H) uint8 GPU tensor"
+        mode, thr, seed, seed_dev, keep = drop.args()
+        # per edge: the source id and the gathered x_j and Q_j rows; per target: its item, the P row, m and the saved rows
+        with _span("nc_std_fwd", nbytes=E * (4 + 8 * H) + N * (16 + 8 * H + (12 * H if save else 0)), flops=(14 if save else 9) * E * H):
+            call("mma_nc_std_fwd", ptr(x_src), x_src.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0),
+                 ptr(graph.rowptr), ptr(graph.col), ptr(graph.items), graph.items.shape[0], graph.n_wave_items,
+                 ptr(graph.hubs) if graph.n_slots else None, graph.hubs.shape[0] if graph.n_slots else 0, ptr(partial), graph.n_slots,
+                 ptr(m), H, ptr(saved), 3 * H if save else 0, N, E, H, host_codes([act]),
+                 mode, thr, seed, seed_dev, graph.edge_base, keep, stream_ptr())
+        ctx.graph, ctx.act, ctx.drop = graph, act, drop
+        ctx.save_for_backward(x_src, P, Q, saved)
+        return m
+
+    @staticmethod
+    def backward(ctx, g):
+        graph, act, drop = ctx.graph, ctx.act, ctx.drop
+        x_src, P, Q, saved = ctx.saved_tensors
+        S, H = x_src.shape
+        N, E = graph.N, graph.E
+        dev = g.device
+        g = g.contiguous()
+        gr = torch.empty((N, H), device=dev, dtype=torch.float32)
+        gP = torch.empty((N, H), device=dev, dtype=torch.float32)
+        gQ = torch.empty((S, H), device=dev, dtype=torch.float32)
+        gx = torch.empty((S, H), device=dev, dtype=torch.float32)
+        n_slots = graph.t_n_slots
+        partial = torch.empty((n_slots, 2 * H), device=dev, dtype=torch.float32) if n_slots else None
+        mode, thr, seed, seed_dev, keep = drop.args()
+        # per edge: target id, edge id and the gathered P, g r and mean rows; per source: its item, x_j and Q_j in, gQ and gx out;
+        # per target (node pass): g and the saved r / coefficient rows in, g r and gP out
+        with _span("nc_std_bwd", nbytes=E * (8 + 12 * H) + S * (16 + 16 * H) + N * 20 * H, flops=13 * E * H):
+            call("mma_nc_std_bwd", ptr(x_src), x_src.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0),
+                 ptr(g), g.stride(0), ptr(saved), saved.stride(0), ptr(gr), H, ptr(gP), H, N,
+                 ptr(graph.t_col), ptr(graph.t_eid), ptr(graph.t_items), graph.t_items.shape[0], graph.t_n_wave_items,
+                 ptr(graph.t_hubs) if n_slots else None, graph.t_hubs.shape[0] if n_slots else 0, ptr(partial), n_slots,
+                 ptr(gQ), H, ptr(gx), H, S, E, H, host_codes([act]), mode, thr, seed, seed_dev, graph.edge_base, keep, stream_ptr())
+        return gx, gP, gQ, None, None, None
+
+
+def nc_std_aggregate(x, P, Q, graph, act=ACT_SIGMOID, drop=None):
+    """The second-moment aggregator of one mask -> m (graph.N, H): the standard deviation, per feature column, of the masked neighbour
+    messages drop(act(P[i] + Q[j])) * x_j of every target i (no self term; an isolated node gives sqrt(1e-5)).
+    x: (graph.n_src, H); P = x[:N] @ W[:H] (N, H), Q = x @ W[H:] (n_src, H); act: ACT_SIGMOID, or ACT_RAW for the raw logits;
+    drop: a DropoutSpec whose explicit keep mask, if any, is (1, E, H)."""
+    return _NCStd.apply(x, P, Q, graph, int(act), drop or DropoutSpec(0.0))
+
+
 def _spmm_call(rowptr, col, val, items, hubs, n_slots, B, rows_per_block, K, bias, out, n_rows, C, n_wave_items=None):
     if K == 1 and items is not None:
         partial = torch.empty((n_slots, C), device=B.device, dtype=torch.float32) if n_slots else None

@@ -10,6 +10,18 @@ Reference behaviour reproduced by default:
   Q7-Q9  max/min are element-wise against x_i, mean divides (x_i+s) by d_i, softmax/softmin == s;
   Q14    reset_parameters: weight/bias U(+-1/sqrt(weight.size(0))), masks U(+-1/sqrt(mask.size(1))).
 Parameters stay owned by the caller (models.py:17-60 creates them and the optimizer holds them).
+
+Extension: the `std` aggregator (strict_reference=False only).  The reference's learnable_std (layers.py:731-771) cannot run - it
+calls the full-graph mean inside its node loop and reduces over the wrong axis - so this is our statement of its evident intent:
+the standard deviation, per feature column c, of the masked neighbour messages of target i.  With add_all[i] the neighbour list
+(multi-edges counted), d = max(len(add_all[i]), 1), W = mask_std, P = x @ W[:H], Q = x @ W[H:]:
+    z_ij  = P[i] + Q[j]
+    a_ij  = sigmoid(z_ij), or z_ij itself when activation == "new_sigmoid"   (layers.py:748-750 discards the activation: Q5)
+    mu_ij = f_ij * a_ij * x_j                 f = dropout keep/scale (DropoutSpec semantics, bits of its own)
+    mean  = (1/d) sum_j mu_ij,   msq = (1/d) sum_j mu_ij^2
+    m_i   = sqrt(max(msq - mean^2, 0) + 1e-5)                                 (EPS = 1e-5: layers.py:735)
+There is no self term x_i (the spread of the messages, not of messages and x_i), and an isolated node gives sqrt(1e-5).  The
+gradient takes relu' = 0 at 0, as torch does.  Kernels: csrc/nc_moments.hip; DESIGN.md "std aggregator".
 """
 import math
 
@@ -31,6 +43,7 @@ _AGG = {
     "softmax": ("softmax", True), "softmin": ("softmin", True),
 }
 _UNUSABLE = ("std", "normalized_mean", "moment_3")   # layers.py:731-851: O(N^2) with a wrong shape / NameError
+_STD_SEED_OFFSET = 0x9E3779B97F4A7C15                # std's dropout seed = the call's seed + this: bits independent of the other masks
 _MASK_NAMES = ["moment_3", "sum", "sum2", "sum3", "sum4", "mean", "mean2", "mean3", "mean4", "max", "max2", "max3",
                "max4", "min", "min2", "min3", "min4", "softmax", "softmin", "std", "normalized_mean"]
 
@@ -101,7 +114,8 @@ class MMA(Module):
         strict_reference=False evaluates the degree scalers with the TRUE degrees len(add_all[i]) instead of the degenerate
         factor 1.0 the reference computes (quirk Q1): `scalers` (default identity, amplification, attenuation - the
         reference's three, scalers.py:64) may also name linear / inverse_linear, and compound_scalers=True chains them like
-        mma_conv.py:181-196 (BASELINE configs[4]: "K=8 aggregators + all scalers")."""
+        mma_conv.py:181-196 (BASELINE configs[4]: "K=8 aggregators + all scalers").  It also makes the `std` aggregator usable
+        (the module docstring defines it); with the default strict_reference=True `std` raises NotImplementedError as before."""
         super().__init__()
         self.activation = activation
         self.k = k
@@ -192,11 +206,20 @@ class MMA(Module):
             acts.append(Fn.ACT_RAW if (rawq and self.activation == "new_sigmoid") else Fn.ACT_SIGMOID)
         return kinds, acts
 
+    def _has_std(self, names):
+        """`std` runs on its own kernel pair (extension); in strict mode it stays in the fused list, where _codes refuses it."""
+        return not self.strict_reference and "std" in names
+
     def _drop(self, names, device=None):
         if self.drop_override is not None:
             return self.drop_override
         if self.graph_capturable and self.dropout > 0 and device is not None:
             n_groups = -(-len(names) // 8)      # one device seed per 8-mask launch group: groups must not share dropout bits
+            if self._has_std(names) or self._has_std(self.aggregator_names):
+                # one more seed (the last) for std's own launch.  Sized from the layer's aggregator list whenever the call's names are
+                # among them, so that forward() and a learnable_<name>() call share one DeviceSeeds instead of re-creating it
+                layout = self.aggregator_names if all(n in self.aggregator_names for n in names) else names
+                n_groups = self._std_seed_slot(layout) + (1 if "std" in layout else 0)
             if self._seeds is None or self._seeds.device != device or self._seeds.n != n_groups:
                 self._seeds = Fn.DeviceSeeds(n_groups, device)
                 self._seed_buf = self._seeds.seeds
@@ -217,9 +240,59 @@ class MMA(Module):
         return Fn.nc_fused_aggregate(input, mm(input, wtop), mm(input, wbot), graph, kinds, acts,
                                      drop or self._drop(names, input.device))
 
+    def _std(self, input, drop=None):
+        """m_std (N, H) by the second-moment kernels.  drop: this mask's own DropoutSpec (explicit keep: (1,E,H))."""
+        if self.strict_reference:
+            self._codes(["std"])                # the reference's learnable_std cannot run: NotImplementedError
+        require_gpu(input)
+        H = input.shape[1]
+        w = self.mask_std
+        act = Fn.ACT_RAW if self.activation == "new_sigmoid" else Fn.ACT_SIGMOID        # layers.py:748-750: raw logits, like Q5
+        if drop is None:       # learnable_std() on its own: std's slot in the layer's seed layout (see _drop)
+            layout = self.aggregator_names if "std" in self.aggregator_names else ["std"]
+            drop = self._std_drop(self._drop(["std"], input.device), 0, self._std_seed_slot(layout))
+        return Fn.nc_std_aggregate(input, mm(input, w[:H]), mm(input, w[H:]), self.graph(input.device), act, drop)
+
+    @staticmethod
+    def _std_seed_slot(names):
+        """Index of std's device seed: behind the seeds of the fused launch groups of the other names."""
+        return -(-len([n for n in names if n != "std"]) // 8)
+
+    @staticmethod
+    def _std_drop(base, pos, slot):
+        """std's DropoutSpec from the call's: its slice of an explicit (K,E,H) mask (pos = its place in the aggregator list), the
+        device seed at `slot` (behind the fused launch groups' seeds), or a host seed of its own."""
+        if base.keep is not None:
+            return Fn.DropoutSpec(base.p, keep=base.keep[pos:pos + 1].contiguous())
+        if base.seed_tensor is not None:
+            # std is mask 0 of its own launch: on a fused group's seed it would draw that group's mask-0 bits
+            if base.seed_tensor.numel() <= slot:
+                raise ValueError("the std aggregator needs a device seed of its own: the DropoutSpec's seed_tensor has %d entries, "
+                                 "std reads entry %d (one per 8-mask launch group, then std's)" % (base.seed_tensor.numel(), slot))
+            return Fn.DropoutSpec(base.p, seed_tensor=base.seed_tensor[slot:])
+        return Fn.DropoutSpec(base.p, seed=base.seed + _STD_SEED_OFFSET)
+
     def _aggregate_all(self, names, input, reduce_k=False):
-        outs = []
+        if self._has_std(names):
+            return self._aggregate_with_std(names, input, reduce_k)
+        return self._aggregate_fused(names, input, self._drop(names, input.device), reduce_k)
+
+    def _aggregate_with_std(self, names, input, reduce_k):
+        """`names` holds std (first occurrence: the aggregator list is a dict's keys): the other masks go through the fused
+        launches as a list of their own, std through its kernel pair; (K,N,H) in the order of `names`, or the sum (N,H)."""
+        pos = names.index("std")
+        others = names[:pos] + names[pos + 1:]
         base = self._drop(names, input.device)
+        m_std = self._std(input, self._std_drop(base, pos, self._std_seed_slot(names)))
+        if not others:
+            return m_std if reduce_k else m_std.unsqueeze(0)
+        if base.keep is not None:       # the other masks' slices of the explicit (K,E,H) mask, in their order
+            base = Fn.DropoutSpec(base.p, keep=torch.cat([base.keep[:pos], base.keep[pos + 1:]], 0))
+        rest = self._aggregate_fused(others, input, base, reduce_k)
+        return rest + m_std if reduce_k else torch.cat([rest[:pos], m_std.unsqueeze(0), rest[pos:]], 0)
+
+    def _aggregate_fused(self, names, input, base, reduce_k=False):
+        outs = []
         for g0 in range(0, len(names), 8):
             grp = names[g0:g0 + 8]
             drop = base
@@ -259,7 +332,7 @@ def _make_learnable(name):
     """learnable_<name>(input, adj): the public per-aggregator methods of layers.py:201-851, same signatures - the max* /
     min* forms carry the reference's (unused) `min_value=-inf` / `max_value=inf` keyword (layers.py:430,540)."""
     def run(self, input):
-        return self._aggregate([name], input)[0]
+        return self._std(input) if name == "std" else self._aggregate([name], input)[0]
     if name.startswith("max"):
         def learnable(self, input, adj, min_value=-math.inf):
             return run(self, input)

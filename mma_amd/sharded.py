@@ -485,6 +485,8 @@ class ShardedMMA(torch.nn.Module):
         assert strict_reference or avg_d is not None, "sharded true-degree scalers need the global degree means (avg_d)"
         self._row_factor = None
         self.plan, self.names, self.activation, self.dropout = plan, list(names), activation, dropout
+        if "std" in self.names:         # mma_amd.MMA's extension runs on the unsharded plan only: its kernels take no halo part lists
+            raise NotImplementedError("the std aggregator is not implemented for the sharded layer (no halo support)")
         self.H, self.C = H, C
         self.lo, self.hi = plan.lo, plan.hi
         dev = torch.device(device)
