@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MMA_ABI_VERSION 37
+#define MMA_ABI_VERSION 38
 #define MMA_MAX_K 8          /* masks fused per launch; more are issued as several launches */
 
 /* combine kinds of the node-classification aggregators (layers.py:201-728) */
@@ -153,6 +153,37 @@ int mma_nc_fused_bwd(
     int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
     int32_t* sync,                               /* optional, as in mma_nc_fused_fwd (shared-gradient form only): ONE launch */
     void* stream);
+
+/* ---- bf16 logit tables (ABI 38) ---------------------------------------------------------------------------------------
+ * mma_nc_fused_fwd_h / mma_nc_fused_bwd_h: the same kernels, arguments, checks and results as mma_nc_fused_fwd / mma_nc_fused_bwd,
+ * with the logit tables P and Q held as bf16 (uint16_t bit patterns, pitches ldp / ldq in ELEMENTS).  Only the per-edge gather of the
+ * logit row changes: K*H*2 bytes instead of K*H*4 (a row is read as 8-byte vectors when H % 4 == 0, the pitches are multiples of 4 and
+ * the tables are 8-byte aligned - the condition that replaces the fp32 tables' 16 bytes - else as scalar 2-byte loads).  A value is
+ * widened with bits << 16, which is exact, so the backward recomputes z = P[i] + Q[j] from exactly what the forward read: the
+ * gradients are those of the function that was evaluated.  x, g, T, crow, gP, gQ and gx stay fp32; gP / gQ are the gradients with
+ * respect to the STORED table values (the rounding of the conversion is treated straight-through).
+ * mma_rows_to_bf16: dst[r, c] = bf16(src[r, c]) for r < rows, c < cols, round to nearest even (inf stays inf, NaN -> 0x7FC0);
+ * 4 columns per lane where cols, lds, ldd are multiples of 4, src is 16-byte and dst 8-byte aligned. */
+int mma_nc_fused_fwd_h(
+    const float* x, int64_t ldx, const uint16_t* P, int64_t ldp, const uint16_t* Q, int64_t ldq,
+    const int32_t* rowptr, const int32_t* col,
+    const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
+    float* partial, int64_t n_slots, float* m, float* m_sum, int64_t ldms, float* T, uint8_t* sel, int64_t ldt,
+    float* crow, int64_t ldc,
+    int64_t N, int64_t E, int32_t H, int32_t K, const uint8_t* kind_host, const uint8_t* act_host,
+    int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
+    int32_t* sync, void* stream);
+int mma_nc_fused_bwd_h(
+    const float* x, int64_t ldx, const uint16_t* P, int64_t ldp, const uint16_t* Q, int64_t ldq,
+    const float* gs, int64_t ldg, const float* g, int64_t ldgg, const float* crow, int64_t ldc, const uint8_t* kind_host,
+    const float* gxs, int64_t ldgx, const float* T, int64_t ldt, float* gP, int64_t ldgp, int64_t n_targets,
+    const int32_t* t_col, const int32_t* t_eid,
+    const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
+    float* partial, int64_t n_slots, float* gQ, int64_t ldgq, float* gx, int64_t ldgxo, float* row_max,
+    int64_t N, int64_t E, int32_t H, int32_t K, const uint8_t* act_host,
+    int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
+    int32_t* sync, void* stream);
+int mma_rows_to_bf16(const float* src, int64_t lds, uint16_t* dst, int64_t ldd, int64_t rows, int64_t cols, void* stream);
 
 /* ---- K1s / K2s (ABI 37): the second-moment ("std") aggregator of the node-classification layer ------------------------
  * An extension (MMA(..., strict_reference=False)): the reference's learnable_std (layers.py:731-771) cannot run, this is its evident

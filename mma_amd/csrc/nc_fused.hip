@@ -23,9 +23,39 @@
 #endif
 namespace mma {
 
-struct NcFwdParams {
+// The logit tables P and Q are held as TT = float, or as bf16 in uint16_t (the `_h` entry points): a compile-time parameter of the
+// param structs and of the K1 / K2b kernels.  A bf16 row is read 4 columns per lane as ONE 8-byte load (VEC = 4) or as scalar 2-byte
+// loads (VEC = 1) and widened with bits << 16, which is exact: everything behind the load is the fp32 code, whatever TT is.
+typedef uint32_t mma_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ Vec<4> widen_bf16x4(uint32_t lo, uint32_t hi) {
+  Vec<4> r;
+  r.v[0] = __uint_as_float(lo << 16); r.v[1] = __uint_as_float(lo & 0xFFFF0000u);
+  r.v[2] = __uint_as_float(hi << 16); r.v[3] = __uint_as_float(hi & 0xFFFF0000u);
+  return r;
+}
+template <int VEC> __device__ __forceinline__ Vec<VEC> ldt(const float* p) { return ldv<VEC>(p); }
+template <int VEC> __device__ __forceinline__ Vec<VEC> ldt_nt(const float* p) { return ldv_nt<VEC>(p); }
+template <int VEC> __device__ __forceinline__ Vec<VEC> ldt(const uint16_t* p) {
+  if constexpr (VEC == 4) {
+    const uint2 t = *reinterpret_cast<const uint2*>(p);
+    return widen_bf16x4(t.x, t.y);
+  } else {
+    Vec<1> r; r.v[0] = __uint_as_float((uint32_t)*p << 16); return r;
+  }
+}
+template <int VEC> __device__ __forceinline__ Vec<VEC> ldt_nt(const uint16_t* p) {
+  if constexpr (VEC == 4) {
+    const mma_u32x2 t = __builtin_nontemporal_load(reinterpret_cast<const mma_u32x2*>(p));
+    return widen_bf16x4(t[0], t[1]);
+  } else {
+    Vec<1> r; r.v[0] = __uint_as_float((uint32_t)__builtin_nontemporal_load(p) << 16); return r;
+  }
+}
+
+template <class TT>
+struct NcFwdParamsT {
   const float* x; int64_t ldx;
-  const float* P; int64_t ldp; const float* Q; int64_t ldq;
+  const TT* P; int64_t ldp; const TT* Q; int64_t ldq;
   const int32_t* rowptr; const int32_t* col;
   const int4* items; int64_t n_items;
   float* partial; int64_t pstride;   // floats per slot = 2*K_total*H
@@ -41,6 +71,7 @@ struct NcFwdParams {
   // one-launch form (nc_fwd_small_kernel): the hub list and the ticket counter of the chunk partials
   const int4* hubs; int64_t n_hubs; unsigned* sync; unsigned n_slots;
 };
+using NcFwdParams = NcFwdParamsT<float>;
 
 // row * pitch as ONE v_mad_u64_u32: rows and pitches are < 2^31 (checked on the host), so the 64-bit product needs neither the
 // sign extension nor the two extra quarter-rate v_mul_lo_u32 the int * int64 form compiles to (3 multiplies per gathered row)
@@ -75,8 +106,8 @@ __device__ __forceinline__ float nc_combine(int kind, float xi, float s, float d
   }
 }
 
-template <int VEC, bool SAVE>
-__device__ __forceinline__ Vec<VEC> nc_fwd_write(const NcFwdParams& p, int node, int k_abs, int c, const Vec<VEC>& xi,
+template <int VEC, bool SAVE, class PP>
+__device__ __forceinline__ Vec<VEC> nc_fwd_write(const PP& p, int node, int k_abs, int c, const Vec<VEC>& xi,
                                                  const Vec<VEC>& s, const Vec<VEC>& t, float deg) {
   Vec<VEC> mo;
   uint32_t codes = 0;
@@ -107,8 +138,8 @@ __device__ __forceinline__ Vec<VEC> nc_fwd_write(const NcFwdParams& p, int node,
 }
 
 // sum over the masks of one launch (K-slices after the first accumulate onto the stored row)
-template <int VEC>
-__device__ __forceinline__ void nc_msum_store(const NcFwdParams& p, int node, int c, Vec<VEC> ms, bool accumulate) {
+template <int VEC, class PP>
+__device__ __forceinline__ void nc_msum_store(const PP& p, int node, int c, Vec<VEC> ms, bool accumulate) {
   float* o = p.msum + (size_t)node * p.ldms + c;
   if (accumulate) {
     const Vec<VEC> prev = ldv<VEC>(o);
@@ -123,15 +154,15 @@ __device__ __forceinline__ void nc_msum_store(const NcFwdParams& p, int node, in
 //                latency chain (item -> indices -> rows -> store) dominates and more items in flight is what pays.
 // DM: dropout mode as a TEMPLATE parameter (MMA_DROP_NONE / HASH / EXPLICIT) - as a run-time field every mask of every edge step
 // carried a scalar branch between the hash and the explicit-mask code, which cut the step into basic blocks
-template <int VEC, bool SAVE>
-__device__ __forceinline__ void nc_fwd_finalize_body(const NcFwdParams& p, const int4* hubs, int64_t n_hubs, const int64_t first, const int64_t step);
+template <int VEC, bool SAVE, class PP>
+__device__ __forceinline__ void nc_fwd_finalize_body(const PP& p, const int4* hubs, int64_t n_hubs, const int64_t first, const int64_t step);
 
 // ONE (the one-launch form, nc_fwd_small_kernel): a wavefront that has written a hub chunk's partial takes a ticket on p.sync after a
 // release fence at device scope (the L2s of the 8 XCDs are not coherent with each other: the fence writes the partial back), and the
 // wavefront that draws the LAST of the n_slots tickets sums the partials of every hub (slot order: same bits as the finalize launch)
 // and leaves the counter at zero.  The chunk items head the longest-first list, so this happens while the short items still run.
-template <int K, int VEC, bool SAVE, int DM, bool MULTI, bool ONE = false>
-__device__ __forceinline__ void nc_fwd_body(const NcFwdParams& p, const int bx, const int nbx) {
+template <int K, int VEC, bool SAVE, int DM, bool MULTI, bool ONE = false, class TT>
+__device__ __forceinline__ void nc_fwd_body(const NcFwdParamsT<TT>& p, const int bx, const int nbx) {
   const DropParams dp = (DM == MMA_DROP_HASH || DM == MMA_DROP_HASH16) ? drop_resolve(p.drop) : p.drop;
   uint32_t mult[K], mult2[K];
 #pragma unroll
@@ -181,7 +212,7 @@ __device__ __forceinline__ void nc_fwd_body(const NcFwdParams& p, const int bx, 
     Vec<VEC> pk[K], acc[K], tac[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      pk[k] = ldv_nt<VEC>(p.P + row_off(node, p.ldp) + (size_t)(p.k_base + k) * p.H + cc);
+      pk[k] = ldt_nt<VEC>(p.P + row_off(node, p.ldp) + (size_t)(p.k_base + k) * p.H + cc);
       acc[k] = vzero<VEC>();
       tac[k] = vzero<VEC>();
     }
@@ -200,10 +231,10 @@ __device__ __forceinline__ void nc_fwd_body(const NcFwdParams& p, const int bx, 
           const int j = __shfl(myj, gbase + (tt[u] & (G - 1)), kWave);
           const int jj = ev[u] ? j : node;   // inactive sub-rows re-read the own row (cached) and are zeroed by SELECTS below
           xj[u] = ldv<VEC>(p.x + row_off(jj, p.ldx) + cc);
-          const float* qrow = p.Q + row_off(jj, p.ldq) + cc;
+          const TT* qrow = p.Q + row_off(jj, p.ldq) + cc;
 #pragma unroll
           for (int k = 0; k < K; ++k)
-            qv[u][k] = ldv<VEC>(qrow + (size_t)(p.k_base + k) * p.H);
+            qv[u][k] = ldt<VEC>(qrow + (size_t)(p.k_base + k) * p.H);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -294,14 +325,14 @@ __device__ __forceinline__ void nc_fwd_body(const NcFwdParams& p, const int bx, 
   }
 }
 
-template <int K, int VEC, bool SAVE, int DM, bool MULTI>
-__global__ __launch_bounds__(kBlock, (K <= 4 ? MMA_MIN_WAVES : 1)) void nc_fwd_kernel(const NcFwdParams p) {
+template <int K, int VEC, bool SAVE, int DM, bool MULTI, class TT = float>
+__global__ __launch_bounds__(kBlock, (K <= 4 ? MMA_MIN_WAVES : 1)) void nc_fwd_kernel(const NcFwdParamsT<TT> p) {
   nc_fwd_body<K, VEC, SAVE, DM, MULTI>(p, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // hub nodes: sum the chunk partials in slot order, then the same epilogue
-template <int VEC, bool SAVE>
-__device__ __forceinline__ void nc_fwd_finalize_body(const NcFwdParams& p, const int4* hubs, int64_t n_hubs, const int64_t first, const int64_t step) {
+template <int VEC, bool SAVE, class PP>
+__device__ __forceinline__ void nc_fwd_finalize_body(const PP& p, const int4* hubs, int64_t n_hubs, const int64_t first, const int64_t step) {
   const int per_row = (p.H + VEC - 1) / VEC;
   const int64_t total = n_hubs * per_row;
   for (int64_t idx = first; idx < total; idx += step) {
@@ -344,8 +375,8 @@ __device__ __forceinline__ void nc_fwd_finalize_body(const NcFwdParams& p, const
     if (SAVE && p.crow && c == 0) p.crow[(size_t)node * p.ldc] = 1.f / deg;
   }
 }
-template <int VEC, bool SAVE>
-__global__ __launch_bounds__(kBlock) void nc_fwd_finalize_kernel(const NcFwdParams p, const int4* hubs, int64_t n_hubs) {
+template <int VEC, bool SAVE, class TT = float>
+__global__ __launch_bounds__(kBlock) void nc_fwd_finalize_kernel(const NcFwdParamsT<TT> p, const int4* hubs, int64_t n_hubs) {
   nc_fwd_finalize_body<VEC, SAVE>(p, hubs, n_hubs, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
@@ -354,14 +385,14 @@ __global__ __launch_bounds__(kBlock) void nc_fwd_finalize_kernel(const NcFwdPara
 // the hub sums are done by the wavefront that stores the last chunk partial (ONE in nc_fwd_body).
 struct NcSmallPlan { int64_t n_wave_items; int blocks_a; };
 
-template <int K, int VEC, bool SAVE, int DM>
-__global__ __launch_bounds__(kBlock, (K <= 4 ? MMA_MIN_WAVES : 1)) void nc_fwd_small_kernel(const NcFwdParams p, const NcSmallPlan sp) {
+template <int K, int VEC, bool SAVE, int DM, class TT = float>
+__global__ __launch_bounds__(kBlock, (K <= 4 ? MMA_MIN_WAVES : 1)) void nc_fwd_small_kernel(const NcFwdParamsT<TT> p, const NcSmallPlan sp) {
   if ((int)blockIdx.x < sp.blocks_a) {
-    NcFwdParams q = p;
+    NcFwdParamsT<TT> q = p;
     q.n_items = sp.n_wave_items;
     nc_fwd_body<K, VEC, SAVE, DM, false, true>(q, (int)blockIdx.x, sp.blocks_a);
   } else {
-    NcFwdParams q = p;
+    NcFwdParamsT<TT> q = p;
     q.items = p.items + sp.n_wave_items; q.n_items = p.n_items - sp.n_wave_items;
     nc_fwd_body<K, VEC, SAVE, DM, true, true>(q, (int)blockIdx.x - sp.blocks_a, (int)gridDim.x - sp.blocks_a);
   }
@@ -459,9 +490,10 @@ __global__ __launch_bounds__(kBlock) void nc_bwd_node_kernel(const NcBwdNodePara
 
 // ------------------------------------------------------------------------------------------------------
 // K2b: edge-level backward over the transposed CSR (grouped by source j)
-struct NcBwdParams {
+template <class TT>
+struct NcBwdParamsT {
   const float* x; int64_t ldx;
-  const float* P; int64_t ldp; const float* Q; int64_t ldq;
+  const TT* P; int64_t ldp; const TT* Q; int64_t ldq;
   const float* gs; int64_t ldg; const float* gxs; int64_t ldgx;
   // SHARED mode (gs == NULL): all masks share one upstream gradient g (n_targets, ldgg); gs_k[i] = g[i] * f(kind_k, code_k[i], 1/d_i)
   // is rebuilt per edge from g[i] and the packed code row K1 wrote, crow[i] = [ 1/d_i,0,0,0 | codes per sel-kind (HQ words) ]
@@ -480,11 +512,12 @@ struct NcBwdParams {
   uint32_t* rowmax;  // optional: max |gQ| (EPI: and |gP|) per source row (see NcBwdNodeParams::rowmax)
   const int4* hubs; int64_t n_hubs; unsigned* sync; unsigned n_slots;      // one-launch form, as in NcFwdParams
 };
+using NcBwdParams = NcBwdParamsT<float>;
 
 // the K2a work of one (node, VEC columns) for the masks [k0, k0 + nk): stores gP, returns the direct term sum_k g * dm/dx_i and
 // the running max |gP|.  Shared by the K2b epilogue and the hub finalize kernel.
-template <int VEC>
-__device__ __forceinline__ Vec<VEC> nc_bwd_epilogue(const NcBwdParams& p, int node, int c, int k0, int nk, float& mx) {
+template <int VEC, class PP>
+__device__ __forceinline__ Vec<VEC> nc_bwd_epilogue(const PP& p, int node, int c, int k0, int nk, float& mx) {
   const Vec<VEC> g = ldv_nt<VEC>(p.g + row_off(node, p.ldgg) + c);
   const float* crow = p.crow + row_off(node, p.ldc);
   const float inv_deg = crow[0];
@@ -516,13 +549,13 @@ __device__ __forceinline__ Vec<VEC> nc_bwd_epilogue(const NcBwdParams& p, int no
   return gxd;
 }
 
-template <int VEC>
-__device__ __forceinline__ void nc_bwd_finalize_body(const NcBwdParams& p, const int4* hubs, int64_t n_hubs, const int64_t first, const int64_t step);
+template <int VEC, class PP>
+__device__ __forceinline__ void nc_bwd_finalize_body(const PP& p, const int4* hubs, int64_t n_hubs, const int64_t first, const int64_t step);
 
 // The lane geometry, the item decode, the keep-factor ladder, the activation pair and the ticket are the same text as in nc_fwd_body,
 // written out in both: as shared functions each of them moved instructions in some kernel ("Shared parts of nc_fused.hip")
-template <int K, int VEC, int DM, bool SHARED, bool MULTI, bool EPI, bool ONE = false>
-__device__ __forceinline__ void nc_bwd_body(const NcBwdParams& p, const int bx, const int nbx) {
+template <int K, int VEC, int DM, bool SHARED, bool MULTI, bool EPI, bool ONE = false, class TT>
+__device__ __forceinline__ void nc_bwd_body(const NcBwdParamsT<TT>& p, const int bx, const int nbx) {
   constexpr bool DROP = DM != MMA_DROP_NONE;
   const DropParams dp = (DM == MMA_DROP_HASH || DM == MMA_DROP_HASH16) ? drop_resolve(p.drop) : p.drop;
   uint32_t mult[K], mult2[K];
@@ -572,7 +605,7 @@ __device__ __forceinline__ void nc_bwd_body(const NcBwdParams& p, const int bx, 
     Vec<VEC> ax = vzero<VEC>();
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      qk[k] = ldv_nt<VEC>(p.Q + row_off(node, p.ldq) + (size_t)(p.k_base + k) * p.H + cc);
+      qk[k] = ldt_nt<VEC>(p.Q + row_off(node, p.ldq) + (size_t)(p.k_base + k) * p.H + cc);
       aq[k] = vzero<VEC>();
     }
 
@@ -609,13 +642,13 @@ __device__ __forceinline__ void nc_bwd_body(const NcBwdParams& p, const int bx, 
               codes[u][k] = crow_codes<VEC>(crow, p.sel_slots, p.k_base + k, p.HQ, cc, 0x02020202u);
             }
           }
-          const float* prow = p.P + row_off(ii, p.ldp) + cc;
+          const TT* prow = p.P + row_off(ii, p.ldp) + cc;
           const float* grow = SHARED ? nullptr : p.gs + row_off(ii, p.ldg) + cc;
 #pragma unroll
           for (int k = 0; k < K; ++k) {
             const size_t o = (size_t)(p.k_base + k) * p.H;
             if (!SHARED) gv[u][k] = ldv<VEC>(grow + o);
-            pv[u][k] = ldv<VEC>(prow + o);
+            pv[u][k] = ldt<VEC>(prow + o);
           }
         }
 #pragma unroll
@@ -754,13 +787,13 @@ __device__ __forceinline__ void nc_bwd_body(const NcBwdParams& p, const int bx, 
   }
 }
 
-template <int K, int VEC, int DM, bool SHARED, bool MULTI, bool EPI>
-__global__ __launch_bounds__(kBlock, (K <= 4 ? MMA_MIN_WAVES : 1)) void nc_bwd_kernel(const NcBwdParams p) {
+template <int K, int VEC, int DM, bool SHARED, bool MULTI, bool EPI, class TT = float>
+__global__ __launch_bounds__(kBlock, (K <= 4 ? MMA_MIN_WAVES : 1)) void nc_bwd_kernel(const NcBwdParamsT<TT> p) {
   nc_bwd_body<K, VEC, DM, SHARED, MULTI, EPI>(p, (int)blockIdx.x, (int)gridDim.x);
 }
 
-template <int VEC>
-__device__ __forceinline__ void nc_bwd_finalize_body(const NcBwdParams& p, const int4* hubs, int64_t n_hubs, const int64_t first, const int64_t step) {
+template <int VEC, class PP>
+__device__ __forceinline__ void nc_bwd_finalize_body(const PP& p, const int4* hubs, int64_t n_hubs, const int64_t first, const int64_t step) {
   const int per_row = (p.H + VEC - 1) / VEC;
   const bool epi = p.T != nullptr;
   const int64_t total = n_hubs * (p.K_total + 1) * per_row;
@@ -824,20 +857,20 @@ __device__ __forceinline__ void nc_bwd_finalize_body(const NcBwdParams& p, const
     }
   }
 }
-template <int VEC>
-__global__ __launch_bounds__(kBlock) void nc_bwd_finalize_kernel(const NcBwdParams p, const int4* hubs, int64_t n_hubs) {
+template <int VEC, class TT = float>
+__global__ __launch_bounds__(kBlock) void nc_bwd_finalize_kernel(const NcBwdParamsT<TT> p, const int4* hubs, int64_t n_hubs) {
   nc_bwd_finalize_body<VEC>(p, hubs, n_hubs, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 // one launch for a small graph's backward (see nc_fwd_small_kernel); shared-gradient form only
-template <int K, int VEC, int DM, bool EPI>
-__global__ __launch_bounds__(kBlock, (K <= 4 ? MMA_MIN_WAVES : 1)) void nc_bwd_small_kernel(const NcBwdParams p, const NcSmallPlan sp) {
+template <int K, int VEC, int DM, bool EPI, class TT = float>
+__global__ __launch_bounds__(kBlock, (K <= 4 ? MMA_MIN_WAVES : 1)) void nc_bwd_small_kernel(const NcBwdParamsT<TT> p, const NcSmallPlan sp) {
   if ((int)blockIdx.x < sp.blocks_a) {
-    NcBwdParams q = p;
+    NcBwdParamsT<TT> q = p;
     q.n_items = sp.n_wave_items;
     nc_bwd_body<K, VEC, DM, true, false, EPI, true>(q, (int)blockIdx.x, sp.blocks_a);
   } else {
-    NcBwdParams q = p;
+    NcBwdParamsT<TT> q = p;
     q.items = p.items + sp.n_wave_items; q.n_items = p.n_items - sp.n_wave_items;
     nc_bwd_body<K, VEC, DM, true, true, EPI, true>(q, (int)blockIdx.x - sp.blocks_a, (int)gridDim.x - sp.blocks_a);
   }
@@ -846,6 +879,8 @@ __global__ __launch_bounds__(kBlock, (K <= 4 ? MMA_MIN_WAVES : 1)) void nc_bwd_s
 // ------------------------------------------------------------------------------------------------------
 // host side
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// a logit table's vector condition: one lane reads 4 elements at once - 16 bytes of fp32, 8 bytes of bf16
+template <class TT> static bool table_aligned(const TT* p) { return (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(TT) - 1)) == 0; }
 
 static int pack_codes(const uint8_t* kind_host, const uint8_t* act_host, int K, uint32_t* kinds, uint32_t* acts) {
   *kinds = 0; *acts = 0;
@@ -929,29 +964,31 @@ template <class F> static void with_form(int vec, int part, F&& f) {
   with_flag(vec == 4, [&](auto v4) { with_flag(part != 0, [&](auto multi) { f(ic<decltype(v4)::value ? 4 : 1>{}, multi); }); });
 }
 
-template <int VEC, bool MULTI>
-static void launch_fwd(int Ks, const NcFwdParams& p, dim3 grid, bool save, int dm, hipStream_t st) {
+template <int VEC, bool MULTI, class TT>
+static void launch_fwd(int Ks, const NcFwdParamsT<TT>& p, dim3 grid, bool save, int dm, hipStream_t st) {
   with_k(Ks, [&](auto k) { with_flag(save, [&](auto sv) { with_dm(dm, [&](auto d) {
-    hipLaunchKernelGGL((nc_fwd_kernel<decltype(k)::value, VEC, decltype(sv)::value, decltype(d)::value, MULTI>), grid, dim3(kBlock), 0, st, p);
+    hipLaunchKernelGGL((nc_fwd_kernel<decltype(k)::value, VEC, decltype(sv)::value, decltype(d)::value, MULTI, TT>), grid, dim3(kBlock), 0, st, p);
   }); }); });
 }
-template <int VEC, bool MULTI>
-static void launch_bwd(int Ks, const NcBwdParams& p, dim3 grid, int dm, hipStream_t st) {
+template <int VEC, bool MULTI, class TT>
+static void launch_bwd(int Ks, const NcBwdParamsT<TT>& p, dim3 grid, int dm, hipStream_t st) {
   with_k(Ks, [&](auto k) { with_dm(dm, [&](auto d) { with_flag(p.gs == nullptr, [&](auto shared) { with_flag(p.T != nullptr, [&](auto epi) {
     constexpr bool SHARED = decltype(shared)::value, EPI = SHARED && decltype(epi)::value;      // the epilogue exists in the shared form only
-    hipLaunchKernelGGL((nc_bwd_kernel<decltype(k)::value, VEC, decltype(d)::value, SHARED, MULTI, EPI>), grid, dim3(kBlock), 0, st, p);
+    hipLaunchKernelGGL((nc_bwd_kernel<decltype(k)::value, VEC, decltype(d)::value, SHARED, MULTI, EPI, TT>), grid, dim3(kBlock), 0, st, p);
   }); }); }); });
 }
 
 // the one-launch form (VEC = 4, hash / no dropout, one K-slice)
-static void launch_fwd_small(int K, const NcFwdParams& p, const NcSmallPlan& sp, dim3 grid, bool save, int dm, hipStream_t st) {
+template <class TT>
+static void launch_fwd_small(int K, const NcFwdParamsT<TT>& p, const NcSmallPlan& sp, dim3 grid, bool save, int dm, hipStream_t st) {
   with_k(K, [&](auto k) { with_flag(save, [&](auto sv) { with_dm<false>(dm, [&](auto d) {
-    hipLaunchKernelGGL((nc_fwd_small_kernel<decltype(k)::value, 4, decltype(sv)::value, decltype(d)::value>), grid, dim3(kBlock), 0, st, p, sp);
+    hipLaunchKernelGGL((nc_fwd_small_kernel<decltype(k)::value, 4, decltype(sv)::value, decltype(d)::value, TT>), grid, dim3(kBlock), 0, st, p, sp);
   }); }); });
 }
-static void launch_bwd_small(int K, const NcBwdParams& p, const NcSmallPlan& sp, dim3 grid, int dm, hipStream_t st) {
+template <class TT>
+static void launch_bwd_small(int K, const NcBwdParamsT<TT>& p, const NcSmallPlan& sp, dim3 grid, int dm, hipStream_t st) {
   with_k(K, [&](auto k) { with_flag(p.T != nullptr, [&](auto epi) { with_dm<false>(dm, [&](auto d) {
-    hipLaunchKernelGGL((nc_bwd_small_kernel<decltype(k)::value, 4, decltype(d)::value, decltype(epi)::value>), grid, dim3(kBlock), 0, st, p, sp);
+    hipLaunchKernelGGL((nc_bwd_small_kernel<decltype(k)::value, 4, decltype(d)::value, decltype(epi)::value, TT>), grid, dim3(kBlock), 0, st, p, sp);
   }); }); });
 }
 // Is the one-launch form possible?  Fills the plan (grid = blocks_a + blocks_b) when it is.  The hub sums are done by ONE wavefront
@@ -1027,8 +1064,10 @@ static void nc_for_slices(Params& p, int64_t n_wave_items, int K, const Geometry
 
 using namespace mma;
 
-extern "C" int mma_nc_fused_fwd(
-    const float* x, int64_t ldx, const float* P, int64_t ldp, const float* Q, int64_t ldq,
+// mma_nc_fused_fwd (TT = float) and mma_nc_fused_fwd_h (TT = uint16_t: bf16 tables, pitches in elements)
+template <class TT>
+static int nc_fused_fwd(
+    const float* x, int64_t ldx, const TT* P, int64_t ldp, const TT* Q, int64_t ldq,
     const int32_t* rowptr, const int32_t* col,
     const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
     float* partial, int64_t n_slots, float* m, float* m_sum, int64_t ldms, float* T, uint8_t* sel, int64_t ldt,
@@ -1052,7 +1091,7 @@ extern "C" int mma_nc_fused_fwd(
   if (int rc = nc_item_alignment(items, hubs)) return rc;
   uint32_t kinds, acts;
   if (int rc = pack_codes(kind_host, act_host, K, &kinds, &acts)) return rc;
-  NcFwdParams p{};
+  NcFwdParamsT<TT> p{};
   if (int rc = make_drop(drop_mode, drop_thr, seed, seed_dev, drop_edge_base, keep, E, &p.drop)) return rc;
   const int dm = (drop_mode == MMA_DROP_HASH && drop_thr == 0) ? MMA_DROP_NONE : p.drop.mode;          // HASH or HASH16 by the threshold
   const bool save = T != nullptr;
@@ -1062,7 +1101,7 @@ extern "C" int mma_nc_fused_fwd(
                 (long long)crow_len);
   }
   const bool v4 = (H % 4 == 0) && (ldx % 4 == 0) && (ldp % 4 == 0) && (ldq % 4 == 0) && (!save || ldt % 4 == 0) && aligned16(x) &&
-                  aligned16(P) && aligned16(Q) && (!m || aligned16(m)) && (!m_sum || (aligned16(m_sum) && ldms % 4 == 0)) &&
+                  table_aligned(P) && table_aligned(Q) && (!m || aligned16(m)) && (!m_sum || (aligned16(m_sum) && ldms % 4 == 0)) &&
                   (!save || (aligned16(T) && (!sel || aligned16(sel)))) && (partial == nullptr || aligned16(partial));
   const Geometry g = geometry(H, v4);
   p.x = x; p.ldx = ldx; p.P = P; p.ldp = ldp; p.Q = Q; p.ldq = ldq; p.rowptr = rowptr; p.col = col;
@@ -1091,13 +1130,52 @@ extern "C" int mma_nc_fused_fwd(
     const dim3 fg((unsigned)elementwise_grid(n_hubs * per_row));
     const int4* hb = reinterpret_cast<const int4*>(hubs);
     with_flag(g.vec == 4, [&](auto v4) { with_flag(save, [&](auto sv) {
-      hipLaunchKernelGGL((nc_fwd_finalize_kernel<decltype(v4)::value ? 4 : 1, decltype(sv)::value>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
+      hipLaunchKernelGGL((nc_fwd_finalize_kernel<decltype(v4)::value ? 4 : 1, decltype(sv)::value, TT>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
     }); });
     if (int rc = check_launch("nc_fwd_finalize_kernel")) return rc;
   }
   return 0;
 }
 
+// The Makefile compiles this file twice, side by side: with MMA_NC_TABLE_F32 into nc_fused.o (the fp32 entry points and kernels) and
+// with MMA_NC_TABLE_BF16 into nc_fused_h.o (the `_h` ones).  With neither defined (a plain compile of the file) it holds both.
+#if !defined(MMA_NC_TABLE_BF16)
+#define MMA_NC_WITH_F32 1
+#endif
+#if !defined(MMA_NC_TABLE_F32)
+#define MMA_NC_WITH_BF16 1
+#endif
+#define NC_FWD_ARGS x, ldx, P, ldp, Q, ldq, rowptr, col, items, n_items, n_wave_items, hubs, n_hubs, partial, n_slots, m, m_sum, ldms, T, sel, ldt, \
+                    crow, ldc, N, E, H, K, kind_host, act_host, drop_mode, drop_thr, seed, seed_dev, drop_edge_base, keep, sync, stream
+#ifdef MMA_NC_WITH_F32
+extern "C" int mma_nc_fused_fwd(
+    const float* x, int64_t ldx, const float* P, int64_t ldp, const float* Q, int64_t ldq,
+    const int32_t* rowptr, const int32_t* col,
+    const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
+    float* partial, int64_t n_slots, float* m, float* m_sum, int64_t ldms, float* T, uint8_t* sel, int64_t ldt,
+    float* crow, int64_t ldc,
+    int64_t N, int64_t E, int32_t H, int32_t K, const uint8_t* kind_host, const uint8_t* act_host,
+    int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
+    int32_t* sync, void* stream) {
+  return nc_fused_fwd<float>(NC_FWD_ARGS);
+}
+#endif
+#ifdef MMA_NC_WITH_BF16
+extern "C" int mma_nc_fused_fwd_h(
+    const float* x, int64_t ldx, const uint16_t* P, int64_t ldp, const uint16_t* Q, int64_t ldq,
+    const int32_t* rowptr, const int32_t* col,
+    const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
+    float* partial, int64_t n_slots, float* m, float* m_sum, int64_t ldms, float* T, uint8_t* sel, int64_t ldt,
+    float* crow, int64_t ldc,
+    int64_t N, int64_t E, int32_t H, int32_t K, const uint8_t* kind_host, const uint8_t* act_host,
+    int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
+    int32_t* sync, void* stream) {
+  return nc_fused_fwd<uint16_t>(NC_FWD_ARGS);
+}
+#endif
+#undef NC_FWD_ARGS
+
+#ifdef MMA_NC_WITH_F32
 extern "C" int64_t mma_nc_crow_floats(int32_t H, int32_t K, const uint8_t* kind_host) {
   if (H < 1 || K < 1 || K > MMA_MAX_K || !kind_host) return -1;
   for (int k = 0; k < K; ++k) if (kind_host[k] > MMA_KIND_SOFTMIN) return -1;
@@ -1134,9 +1212,11 @@ extern "C" int mma_nc_bwd_node(
   else hipLaunchKernelGGL((nc_bwd_node_kernel<1>), grid, dim3(kBlock), 0, st, p);
   return check_launch("nc_bwd_node_kernel");
 }
+#endif
 
-extern "C" int mma_nc_fused_bwd(
-    const float* x, int64_t ldx, const float* P, int64_t ldp, const float* Q, int64_t ldq,
+template <class TT>
+static int nc_fused_bwd(
+    const float* x, int64_t ldx, const TT* P, int64_t ldp, const TT* Q, int64_t ldq,
     const float* gs, int64_t ldg, const float* g, int64_t ldgg, const float* crow, int64_t ldc, const uint8_t* kind_host,
     const float* gxs, int64_t ldgx, const float* T, int64_t ldt, float* gP, int64_t ldgp, int64_t n_targets,
     const int32_t* t_col, const int32_t* t_eid,
@@ -1164,13 +1244,13 @@ extern "C" int mma_nc_fused_bwd(
   if (int rc = nc_item_alignment(items, hubs)) return rc;
   uint32_t kinds, acts;
   if (int rc = pack_codes(shared ? kind_host : nullptr, act_host, K, &kinds, &acts)) return rc;
-  NcBwdParams p{};
+  NcBwdParamsT<TT> p{};
   if (int rc = make_drop(drop_mode, drop_thr, seed, seed_dev, drop_edge_base, keep, E, &p.drop)) return rc;
   const int dm = (drop_mode == MMA_DROP_HASH && drop_thr == 0) ? MMA_DROP_NONE : p.drop.mode;          // HASH or HASH16 by the threshold
   const bool v4 = (H % 4 == 0) && (ldx % 4 == 0) && (ldp % 4 == 0) && (ldq % 4 == 0) && (epi || (ldgx % 4 == 0 && aligned16(gxs))) && (ldgq % 4 == 0) &&
                   (shared ? (ldgg % 4 == 0 && aligned16(g) && ldc % 4 == 0 && aligned16(crow)) : (ldg % 4 == 0 && aligned16(gs))) &&
                   (!epi || (ldt % 4 == 0 && aligned16(T) && ldgp % 4 == 0 && aligned16(gP))) &&
-                  (ldgxo % 4 == 0) && aligned16(x) && aligned16(P) && aligned16(Q) &&
+                  (ldgxo % 4 == 0) && aligned16(x) && table_aligned(P) && table_aligned(Q) &&
                   aligned16(gQ) && aligned16(gx) && (partial == nullptr || aligned16(partial));
   const Geometry geo = geometry(H, v4);
   p.x = x; p.ldx = ldx; p.P = P; p.ldp = ldp; p.Q = Q; p.ldq = ldq; p.gs = gs; p.ldg = ldg; p.gxs = gxs; p.ldgx = ldgx;
@@ -1205,9 +1285,42 @@ extern "C" int mma_nc_fused_bwd(
     const dim3 fg((unsigned)elementwise_grid(n_hubs * (K + 1) * per_row));
     const int4* hb = reinterpret_cast<const int4*>(hubs);
     with_flag(geo.vec == 4, [&](auto v4) {
-      hipLaunchKernelGGL((nc_bwd_finalize_kernel<decltype(v4)::value ? 4 : 1>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
+      hipLaunchKernelGGL((nc_bwd_finalize_kernel<decltype(v4)::value ? 4 : 1, TT>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
     });
     if (int rc = check_launch("nc_bwd_finalize_kernel")) return rc;
   }
   return 0;
 }
+
+#define NC_BWD_ARGS x, ldx, P, ldp, Q, ldq, gs, ldg, g, ldgg, crow, ldc, kind_host, gxs, ldgx, T, ldt, gP, ldgp, n_targets, t_col, t_eid, items, n_items, \
+                    n_wave_items, hubs, n_hubs, partial, n_slots, gQ, ldgq, gx, ldgxo, row_max, N, E, H, K, act_host, drop_mode, drop_thr, seed, seed_dev, \
+                    drop_edge_base, keep, sync, stream
+#ifdef MMA_NC_WITH_F32
+extern "C" int mma_nc_fused_bwd(
+    const float* x, int64_t ldx, const float* P, int64_t ldp, const float* Q, int64_t ldq,
+    const float* gs, int64_t ldg, const float* g, int64_t ldgg, const float* crow, int64_t ldc, const uint8_t* kind_host,
+    const float* gxs, int64_t ldgx, const float* T, int64_t ldt, float* gP, int64_t ldgp, int64_t n_targets,
+    const int32_t* t_col, const int32_t* t_eid,
+    const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
+    float* partial, int64_t n_slots, float* gQ, int64_t ldgq, float* gx, int64_t ldgxo, float* row_max,
+    int64_t N, int64_t E, int32_t H, int32_t K, const uint8_t* act_host,
+    int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
+    int32_t* sync, void* stream) {
+  return nc_fused_bwd<float>(NC_BWD_ARGS);
+}
+#endif
+#ifdef MMA_NC_WITH_BF16
+extern "C" int mma_nc_fused_bwd_h(
+    const float* x, int64_t ldx, const uint16_t* P, int64_t ldp, const uint16_t* Q, int64_t ldq,
+    const float* gs, int64_t ldg, const float* g, int64_t ldgg, const float* crow, int64_t ldc, const uint8_t* kind_host,
+    const float* gxs, int64_t ldgx, const float* T, int64_t ldt, float* gP, int64_t ldgp, int64_t n_targets,
+    const int32_t* t_col, const int32_t* t_eid,
+    const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
+    float* partial, int64_t n_slots, float* gQ, int64_t ldgq, float* gx, int64_t ldgxo, float* row_max,
+    int64_t N, int64_t E, int32_t H, int32_t K, const uint8_t* act_host,
+    int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
+    int32_t* sync, void* stream) {
+  return nc_fused_bwd<uint16_t>(NC_BWD_ARGS);
+}
+#endif
+#undef NC_BWD_ARGS

@@ -206,3 +206,52 @@ extern "C" int mma_edge_fold_bwd(const float* We, int64_t ldw, const float* Wenc
                      static_cast<hipStream_t>(stream), p);
   return check_launch("edge_fold_bwd_kernel");
 }
+
+// ---- fp32 rows -> bf16 rows: the logit tables [P | Q] of the NC layer's bf16 form (mma_nc_fused_fwd_h / _bwd_h), converted ONCE per
+// call from the forward GEMM's (N, 2*K*H) output - N rows, against the E per-edge gathers that then read half the bytes.  Round to
+// nearest even on the bit pattern; inf stays inf, a NaN becomes the quiet NaN 0x7FC0 (what torch's fp32 -> bfloat16 conversion gives).
+namespace mma {
+
+typedef uint32_t mma_pack_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t bf16_rne(float f) {
+  const uint32_t b = __float_as_uint(f);
+  if ((b & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;
+  return (b + 0x7FFFu + ((b >> 16) & 1u)) >> 16;       // a carry out of the mantissa moves into the exponent (up to inf), as it must
+}
+
+template <bool V4>
+__global__ __launch_bounds__(kBlock) void rows_to_bf16_kernel(const float* __restrict__ src, int64_t lds, uint16_t* __restrict__ dst, int64_t ldd,
+                                                              int64_t rows, int64_t cols) {
+  const int64_t per_row = V4 ? cols / 4 : cols;
+  const int64_t total = rows * per_row;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / per_row, c = (i - r * per_row) * (V4 ? 4 : 1);
+    if (V4) {
+      // both sides are touched once by this kernel: streaming (`nt`) load and store
+      const mma_f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const mma_f32x4*>(src + r * lds + c));
+      mma_pack_u32x2 o;
+      o[0] = bf16_rne(v[0]) | (bf16_rne(v[1]) << 16);
+      o[1] = bf16_rne(v[2]) | (bf16_rne(v[3]) << 16);
+      __builtin_nontemporal_store(o, reinterpret_cast<mma_pack_u32x2*>(dst + r * ldd + c));
+    } else {
+      dst[r * ldd + c] = (uint16_t)bf16_rne(src[r * lds + c]);
+    }
+  }
+}
+
+}  // namespace mma
+
+extern "C" int mma_rows_to_bf16(const float* src, int64_t lds, uint16_t* dst, int64_t ldd, int64_t rows, int64_t cols, void* stream) {
+  MMA_REQUIRE(rows >= 0 && cols >= 0 && rows < (1LL << 31) && cols < (1LL << 31), "rows=%lld cols=%lld out of range", (long long)rows, (long long)cols);
+  MMA_REQUIRE(lds >= cols && ldd >= cols, "row pitch too small: lds=%lld ldd=%lld", (long long)lds, (long long)ldd);
+  if (rows == 0 || cols == 0) return 0;
+  MMA_REQUIRE(src && dst, "NULL argument");
+  const bool v4 = cols % 4 == 0 && lds % 4 == 0 && ldd % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0 && (reinterpret_cast<uintptr_t>(dst) & 7u) == 0;
+  const int64_t total = rows * (v4 ? cols / 4 : cols);
+  int64_t blocks = (total + kBlock - 1) / kBlock;
+  if (blocks > 8 * kMaxGrid) blocks = 8 * kMaxGrid;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (v4) hipLaunchKernelGGL(rows_to_bf16_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, st, src, lds, dst, ldd, rows, cols);
+  else hipLaunchKernelGGL(rows_to_bf16_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, st, src, lds, dst, ldd, rows, cols);
+  return check_launch("rows_to_bf16_kernel");
+}

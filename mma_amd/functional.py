@@ -73,6 +73,35 @@ class DropoutSpec:
         return self.mode, self.thr, self.seed, ptr(self.seed_tensor), ptr(self.keep)
 
 
+LOGIT_DTYPES = (torch.float32, torch.bfloat16)     # storage of the logit tables P, Q of the fused NC kernels
+
+
+def check_logit_dtype(logit_dtype):
+    if logit_dtype not in LOGIT_DTYPES:
+        raise ValueError("logit_dtype has to be torch.float32 or torch.bfloat16, but got %r" % (logit_dtype,))
+    return logit_dtype
+
+
+def _nc_entry(name, P, Q):
+    """The entry point for the tables' storage type: `name` for fp32 tables, `name`_h for bf16 ones (ABI 38)."""
+    if P.dtype != Q.dtype:
+        raise ValueError("the logit tables P and Q must share a dtype, got %s and %s" % (P.dtype, Q.dtype))
+    check_logit_dtype(P.dtype)
+    return name if P.dtype == torch.float32 else name + "_h"
+
+
+def rows_to_bf16(src, out=None):
+    """(rows, cols) fp32 -> bf16, round to nearest even, in one launch (mma_rows_to_bf16); src / out may be row-pitched."""
+    rows, cols = src.shape
+    assert src.dtype == torch.float32 and src.stride(1) == 1
+    if out is None:
+        out = torch.empty((rows, cols), device=src.device, dtype=torch.bfloat16)
+    assert out.dtype == torch.bfloat16 and out.shape == src.shape and out.stride(1) == 1
+    with _span("rows_to_bf16", nbytes=6 * rows * cols):
+        call("mma_rows_to_bf16", ptr(src), src.stride(0), ptr(out), out.stride(0), rows, cols, stream_ptr())
+    return out
+
+
 def crow_floats(H, kinds):
     return _lib.query("mma_nc_crow_floats", H, len(kinds), host_codes(kinds))
 
@@ -80,12 +109,14 @@ def crow_floats(H, kinds):
 def nc_fwd_launch(x_src, P, Q, graph, kinds, acts, drop, reduce_k, save, shared=None):
     """K1 on prepared operands -> (m or msum, T, sel, crow).  No autograd; shared by _NCFused and the sharded layer.
     shared (default: reduce_k and SHARED_GRAD_BWD): the backward will take the shared-gradient form, so the selection state is
-    saved as the packed code rows `crow` (N, ldc) K2b gathers per edge instead of the (N,K*H) byte array `sel`."""
+    saved as the packed code rows `crow` (N, ldc) K2b gathers per edge instead of the (N,K*H) byte array `sel`.
+    P and Q are both fp32, or both bf16 (the `_h` entry point: half the bytes of the per-edge logit gather)."""
+    entry = _nc_entry("mma_nc_fused_fwd", P, Q)
     K = len(kinds)
     S, H = x_src.shape
     N = graph.N
     shared = (reduce_k and SHARED_GRAD_BWD) if shared is None else shared
-    assert x_src.dtype == torch.float32 and P.dtype == torch.float32 and Q.dtype == torch.float32
+    assert x_src.dtype == torch.float32
     assert S == graph.n_src and P.shape == (N, K * H) and Q.shape == (S, K * H) and 1 <= K <= 8
     assert x_src.is_contiguous() and P.stride(1) == 1 and Q.stride(1) == 1
     dev = x_src.device
@@ -104,7 +135,7 @@ def nc_fwd_launch(x_src, P, Q, graph, kinds, acts, drop, reduce_k, save, shared=
             tuple(drop.keep.shape) == (K, graph.E, H), "explicit keep mask must be a contiguous (K,E,H) uint8 GPU tensor"
     mode, thr, seed, seed_dev, keep = drop.args()
     with _span("nc_fused_fwd"):
-        call("mma_nc_fused_fwd", ptr(x_src), x_src.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0),
+        call(entry, ptr(x_src), x_src.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0),
              ptr(graph.rowptr), ptr(graph.col), ptr(graph.items), graph.items.shape[0], graph.n_wave_items,
              ptr(graph.hubs) if graph.n_slots else None, graph.hubs.shape[0], ptr(partial), graph.n_slots,
              ptr(m), ptr(msum), H, ptr(T), ptr(sel), K * H, ptr(crow), crow.stride(0) if crow is not None else 0,
@@ -133,14 +164,16 @@ def nc_bwd_node_launch(g, reduce_k, sel, crow, T, graph, kinds, H, shared, gP=No
 
 def nc_bwd_edges_launch(x_src, P, Q, gs, g, crow, gxs, graph, kinds, acts, drop, gQ, gx, partial, part=None, row_max=None, T=None, gP=None):
     """K2b over the transposed CSR; `part` = (items, n_wave_items, hubs) restricts it to a subset of the sources.
-    gs given: materialised dL/ds rows; else the shared-gradient form on (g, crow); with T and gP: K2a fused into the epilogue."""
+    gs given: materialised dL/ds rows; else the shared-gradient form on (g, crow); with T and gP: K2a fused into the epilogue.
+    P and Q: the tables the forward read, fp32 or bf16 (z is recomputed from the same stored values)."""
+    entry = _nc_entry("mma_nc_fused_bwd", P, Q)
     K = len(acts)
     S, H = x_src.shape
     items, n_wave, hubs = part if part is not None else (graph.t_items, graph.t_n_wave_items, graph.t_hubs)
     shared = gs is None
     mode, thr, seed, seed_dev, keep = drop.args()
     with _span("nc_fused_bwd"):
-        call("mma_nc_fused_bwd", ptr(x_src), x_src.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0),
+        call(entry, ptr(x_src), x_src.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0),
              ptr(gs), K * H, ptr(g) if shared else None, g.stride(0) if shared else 0,
              ptr(crow) if shared else None, crow.stride(0) if shared else 0, host_codes(kinds) if shared else None,
              ptr(gxs), H, ptr(T), K * H if T is not None else 0, ptr(gP), gP.stride(0) if gP is not None else 0, graph.N,
@@ -173,10 +206,13 @@ def nc_bwd_plan(x_src, P, Q, g, T, sel, crow, graph, kinds, acts, drop, reduce_k
 class _NCFused(torch.autograd.Function):
     """m[k] = combine_k(x_i, sum_j drop(act_k(P_k[i] + Q_k[j])) * x_j)   (K1 forward, K2a + K2b backward).
     reduce_k: return sum_k m[k] (N,H) instead of (K,N,H) - all MMA.forward needs; backward then takes the
-    shared-gradient form (one (N,H) upstream gradient for all masks)."""
+    shared-gradient form (one (N,H) upstream gradient for all masks).
+    logit_dtype torch.bfloat16: fp32 P / Q are converted once (mma_rows_to_bf16) and the kernels gather the bf16 tables, which are also
+    what is saved; gP / gQ come back in fp32 as the gradients with respect to the stored values (straight-through).  P / Q may also be
+    given in bf16 themselves (autograd then casts their gradients to bf16)."""
 
     @staticmethod
-    def forward(ctx, x_src, P, Q, graph, kinds, acts, drop, reduce_k):
+    def forward(ctx, x_src, P, Q, graph, kinds, acts, drop, reduce_k, logit_dtype=None):
         # x_src: (n_src,H) feature table; its first N rows are the targets (n_src > N only in the sharded path,
         # where the tail holds halo rows).  P: (N,K*H) = x_src[:N] @ [W_k[:H]..], Q: (n_src,K*H) = x_src @ [W_k[H:]..]
         require_gpu(x_src, P, Q)
@@ -185,6 +221,11 @@ class _NCFused(torch.autograd.Function):
             P = P.contiguous()
         if Q.stride(1) != 1:
             Q = Q.contiguous()
+        _nc_entry("mma_nc_fused_fwd", P, Q)
+        if logit_dtype is not None and check_logit_dtype(logit_dtype) != P.dtype:
+            if logit_dtype != torch.bfloat16:
+                raise ValueError("bf16 logit tables cannot be widened back: pass logit_dtype=None or torch.bfloat16 with them")
+            P, Q = rows_to_bf16(P), rows_to_bf16(Q)
         out, T, sel, crow = nc_fwd_launch(x_src, P, Q, graph, kinds, acts, drop, reduce_k, any(ctx.needs_input_grad[:3]))
         ctx.graph, ctx.kinds, ctx.acts, ctx.drop, ctx.reduce_k = graph, kinds, acts, drop, reduce_k
         ctx.save_for_backward(x_src, P, Q, T, sel, crow)
@@ -200,7 +241,7 @@ class _NCFused(torch.autograd.Function):
         gx = torch.empty((S, H), device=g.device, dtype=torch.float32)
         gP, run = nc_bwd_plan(x_src, P, Q, g, T, sel, crow, graph, kinds, acts, drop, reduce_k, None, gQ, gx)
         run()
-        return gx, gP, gQ, None, None, None, None, None
+        return gx, gP, gQ, None, None, None, None, None, None
 
 
 class _NCLocalLayer(torch.autograd.Function):
@@ -208,7 +249,7 @@ class _NCLocalLayer(torch.autograd.Function):
     blocks of ONE (N,2*K*H) buffer - one forward GEMM, one dL/dx GEMM over the concatenated reduction, one dW GEMM."""
 
     @staticmethod
-    def forward(ctx, x, wtop, wbot, graph, kinds, acts, drop):
+    def forward(ctx, x, wtop, wbot, graph, kinds, acts, drop, logit_dtype=torch.float32):
         from .dense import mm_into
         require_gpu(x)
         x = x.contiguous()
@@ -221,6 +262,8 @@ class _NCLocalLayer(torch.autograd.Function):
         need = any(ctx.needs_input_grad[:3])
         box = [] if need else None                                          # row maxima of x, when the forward GEMM forms them: the
         mm_into(x, wcat, PQ, row_max_box=box)                               # weight-gradient product's row scales (three-product TN form)
+        if check_logit_dtype(logit_dtype) == torch.bfloat16:
+            PQ = rows_to_bf16(PQ)       # N rows converted once; K1 and K2b gather (and the backward keeps) the half-size tables
         msum, T, sel, crow = nc_fwd_launch(x, PQ[:, :KH], PQ[:, KH:], graph, kinds, acts, drop, True, need)
         ctx.graph, ctx.kinds, ctx.acts, ctx.drop = graph, kinds, acts, drop
         ctx.save_for_backward(x, PQ, T, sel, crow, wcat, box[0] if box else None)
@@ -245,15 +288,19 @@ class _NCLocalLayer(torch.autograd.Function):
         rows_mm_add_(gx, gPQ, wcat.t(), row_max)                             # direct + through P and Q in one GEMM (C += A B)
         gw = xt_g(x, gPQ, x_row_max, row_max) if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) else None
         if ctx.cat_given:
-            return gx, gw, None, None, None, None, None
-        return gx, (gw[:, :KH] if gw is not None else None), (gw[:, KH:] if gw is not None else None), None, None, None, None
+            return gx, gw, None, None, None, None, None, None
+        return gx, (gw[:, :KH] if gw is not None else None), (gw[:, KH:] if gw is not None else None), None, None, None, None, None
 
 
-def nc_local_layer(x, wtop, wbot, graph, kinds, acts, drop=None):
+def nc_local_layer(x, wtop, wbot, graph, kinds, acts, drop=None, logit_dtype=torch.float32):
     """sum_k m_k (graph.N, H) straight from the features and the concatenated mask weights (unsharded graphs).
-    wbot=None: `wtop` is already [Wtop | Wbot] (H, 2*K*H), e.g. from mask_weights()."""
+    wbot=None: `wtop` is already [Wtop | Wbot] (H, 2*K*H), e.g. from mask_weights().
+    logit_dtype=torch.bfloat16: the [P | Q] buffer of the forward GEMM is rounded to bf16 once (mma_rows_to_bf16) and the bf16 buffer
+    is what the fused kernels gather and what is saved for the backward (half the saved activation); every sum, x and every gradient
+    stay fp32, and the gradients are the exact ones of the function evaluated on the rounded logits."""
+    check_logit_dtype(logit_dtype)
     assert graph.n_src == graph.N
-    return _NCLocalLayer.apply(x, wtop, wbot, graph, tuple(kinds), tuple(acts), drop or DropoutSpec(0.0))
+    return _NCLocalLayer.apply(x, wtop, wbot, graph, tuple(kinds), tuple(acts), drop or DropoutSpec(0.0), logit_dtype)
 
 
 class DeviceSeeds:
@@ -313,13 +360,14 @@ def mask_weights(masks):
     return _MaskWeights.apply(*masks)
 
 
-def nc_fused_aggregate(x, P, Q, graph, kinds, acts, drop=None, reduce_k=False):
+def nc_fused_aggregate(x, P, Q, graph, kinds, acts, drop=None, reduce_k=False, logit_dtype=None):
     """Fused K-mask aggregation (K <= 8 per call) -> m (K, graph.N, H), or sum_k m[k] (graph.N, H) with reduce_k.
 
     x: (graph.n_src, H) feature table whose first graph.N rows are the targets; P = x[:N] @ Wtop (N, K*H),
     Q = x @ Wbot (n_src, K*H) with Wtop/Wbot the column-concatenated top/bottom halves of the K mask weights;
-    kinds/acts: MMA_KIND_* / MMA_ACT_* codes per mask."""
-    return _NCFused.apply(x, P, Q, graph, tuple(kinds), tuple(acts), drop or DropoutSpec(0.0), bool(reduce_k))
+    kinds/acts: MMA_KIND_* / MMA_ACT_* codes per mask.  logit_dtype: None keeps the tables as given (fp32, or bf16 both);
+    torch.bfloat16 rounds fp32 tables once and gathers the bf16 copies (see _NCFused)."""
+    return _NCFused.apply(x, P, Q, graph, tuple(kinds), tuple(acts), drop or DropoutSpec(0.0), bool(reduce_k), logit_dtype)
 
 
 class _NCStd(torch.autograd.Function):

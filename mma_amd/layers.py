@@ -109,14 +109,21 @@ class MMA(Module):
                  weight_mean2, weight_mean3, weight_mean4, weight_max, weight_max2, weight_max3,
                  weight_max4, weight_min, weight_min2, weight_min3, weight_min4, weight_softmax,
                  weight_softmin, weight_std, weight_normalized_mean, dropout, aggregator_list, device,
-                 chunk=DEFAULT_CHUNK, strict_reference=True, scalers=None, compound_scalers=False, avg_d=None):
+                 chunk=DEFAULT_CHUNK, strict_reference=True, scalers=None, compound_scalers=False, avg_d=None,
+                 logit_dtype=torch.float32):
         """Positional arguments: the reference's (layers.py:57-61).  Keyword extensions (defaults = reference behaviour):
         strict_reference=False evaluates the degree scalers with the TRUE degrees len(add_all[i]) instead of the degenerate
         factor 1.0 the reference computes (quirk Q1): `scalers` (default identity, amplification, attenuation - the
         reference's three, scalers.py:64) may also name linear / inverse_linear, and compound_scalers=True chains them like
         mma_conv.py:181-196 (BASELINE configs[4]: "K=8 aggregators + all scalers").  It also makes the `std` aggregator usable
-        (the module docstring defines it); with the default strict_reference=True `std` raises NotImplementedError as before."""
+        (the module docstring defines it); with the default strict_reference=True `std` raises NotImplementedError as before.
+        logit_dtype (either strict_reference mode: a storage choice, not a semantic extension): torch.float32 (default, the path as
+        it always was) or torch.bfloat16 - the mask logit tables P = x W[:H], Q = x W[H:] of the fused aggregators are rounded to
+        bf16 once per call and the kernels gather, and the backward keeps, the half-size tables.  Only z = P[i] + Q[j] sees the
+        rounding; x, every sum and every gradient stay fp32.  Applies to forward() and every fused learnable_<name>(), under hash and
+        explicit dropout and under graph_capturable; the `std` aggregator and ShardedMMA keep fp32 tables."""
         super().__init__()
+        self.logit_dtype = Fn.check_logit_dtype(logit_dtype)
         self.activation = activation
         self.k = k
         self.in_features = in_features
@@ -235,10 +242,11 @@ class MMA(Module):
         # [x_i || x_j] @ W_k  ==  x_i @ W_k[:H] + x_j @ W_k[H:]: dense GEMMs (matrix cores) shared by all K masks
         graph = self.graph(input.device)
         if reduce_k:
-            return Fn.nc_local_layer(input, Fn.mask_weights(masks), None, graph, kinds, acts, drop or self._drop(names, input.device))
+            return Fn.nc_local_layer(input, Fn.mask_weights(masks), None, graph, kinds, acts, drop or self._drop(names, input.device),
+                                     logit_dtype=self.logit_dtype)
         wtop, wbot = torch.cat([w[:H] for w in masks], 1), torch.cat([w[H:] for w in masks], 1)      # (H, K*H) each
         return Fn.nc_fused_aggregate(input, mm(input, wtop), mm(input, wbot), graph, kinds, acts,
-                                     drop or self._drop(names, input.device))
+                                     drop or self._drop(names, input.device), logit_dtype=self.logit_dtype)
 
     def _std(self, input, drop=None):
         """m_std (N, H) by the second-moment kernels.  drop: this mask's own DropoutSpec (explicit keep: (1,E,H))."""
