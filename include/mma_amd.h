@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MMA_ABI_VERSION 38
+#define MMA_ABI_VERSION 39
 #define MMA_MAX_K 8          /* masks fused per launch; more are issued as several launches */
 
 /* combine kinds of the node-classification aggregators (layers.py:201-728) */
@@ -304,6 +304,18 @@ int64_t mma_pack_f16x2_k256_bytes(int64_t M);
 int mma_pack_f16x2_k256(const float* A, int64_t lda, int64_t M, void* Ap, int32_t* sce, float* row_max, void* stream);
 int mma_gemm_f16x2_k256p(const void* Ap, const int32_t* sce, const void* Bt2, const float* col_unscale, float* C, int64_t ldc,
                          int64_t M, int32_t N, void* stream);
+/* ABI 39: the three column-group forms above with a bf16 result written from the kernel's epilogue (the logit tables [P|Q] of
+ * MMA(..., logit_dtype=torch.bfloat16): no fp32 (M, N) buffer and no mma_rows_to_bf16 pass over it).  Parameters, checks, G2 choice and
+ * launch of the fp32 twin; C is (M, N) bf16 bit patterns and ldc counts bf16 ELEMENTS.  Every result is the fp32 twin's value rounded to
+ * nearest even (inf stays inf, a NaN becomes the quiet NaN 0x7FC0): bit for bit what mma_rows_to_bf16 makes of the twin's output.
+ * Alignment: the kernels store single 2-byte elements, so C needs 2-byte alignment only and any ldc >= N (< 2^24) is taken; an odd C is
+ * refused as a misaligned argument.  Rows past M are never written, nor are the columns between N and ldc. */
+int mma_gemm_f16x2_k_h(const float* A, int64_t lda, const void* Bt2, const float* col_unscale, uint16_t* C, int64_t ldc,
+                       float* a_row_max, int64_t M, int32_t N, int32_t K, void* stream);
+int mma_gemm_f16x2_k256_h(const float* A, int64_t lda, const float* row_max, const void* Bt2, const float* col_unscale, uint16_t* C,
+                          int64_t ldc, int64_t M, int32_t N, void* stream);
+int mma_gemm_f16x2_k256p_h(const void* Ap, const int32_t* sce, const void* Bt2, const float* col_unscale, uint16_t* C, int64_t ldc,
+                           int64_t M, int32_t N, void* stream);
 /* The same three-product form for N = 128 and a long reduction (dL/dx += [gP|gQ] [Wtop|Wbot]^T, K % 64 == 0): the row scales
  * cannot be formed in the kernel (a row is consumed in 64-wide chunks), so the caller passes row_max (M,) >= the maximum
  * |a| of every row (the backward kernels produce it: mma_nc_bwd_node / mma_nc_fused_bwd); 0 marks an all-zero row.

@@ -203,6 +203,14 @@ __device__ __forceinline__ uint32_t up16_nonneg(const float m) {
   return b >= 0x7F800000u ? b >> 16 : (b + 0xFFFFu) >> 16;
 }
 
+// fp32 -> the 16 bits of a bf16, round to nearest even on the bit pattern: inf stays inf, a NaN becomes the quiet NaN 0x7FC0 (torch's
+// conversion).  The ONE rounding of the bf16 logit tables: mma_rows_to_bf16 and the epilogue of the bf16-output GEMMs give the same bits.
+__device__ __forceinline__ uint32_t bf16_rne(float f) {
+  const uint32_t b = __float_as_uint(f);
+  if ((b & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;
+  return (b + 0x7FFFu + ((b >> 16) & 1u)) >> 16;       // a carry out of the mantissa moves into the exponent (up to inf), as it must
+}
+
 __host__ inline int ilog2_ceil(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 }  // namespace mma

@@ -377,11 +377,24 @@ __device__ __forceinline__ F16x2 split_f16x2(const float4 a, const float4 b, con
   }
   return r;
 }
+// The output type CT of the column-group kernels: float, or uint16_t = bf16 (ABI 39: the logit tables [P|Q] of the NC layer's bf16 form leave
+// the forward product in bf16, without the fp32 buffer and the conversion pass over it).  cg_out: a finished fp32 result as the tile keeps it
+// until its stores - itself, or its bf16 bits (round to nearest even: common.h, the one mma_rows_to_bf16 uses) in the low half of the register.
+template <class CT> __device__ __forceinline__ float cg_out(const float v) {
+  if constexpr (sizeof(CT) == 4) return v;
+  else return __uint_as_float(bf16_rne(v));
+}
 // Register r of a finished tile of the column-group kernels -> its row of C, streaming (nt): crow = descriptor of the wave's rows, c_off =
-// this lane's (4h, r31) in floats, pcol = the tile's first column in bytes.  Both the store behind a k-step and the final epilogue.
+// this lane's (4h, r31) in elements, pcol = the tile's first column in bytes.  Both the store behind a k-step and the final epilogue.
+// bf16: one 2-byte store per register - an instruction writes two 64-byte row segments (fp32: two of 128), 16 stores per tile as before.
+template <class CT>
 __device__ __forceinline__ void cg_store(const float v, const __amdgpu_buffer_rsrc_t crow, const uint32_t c_off, const int r, const int ldc,
                                          const uint32_t pcol) {
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), crow, c_off * 4u, (uint32_t)(acc_row(r) * ldc) * 4u + pcol, kCgStoreAux);
+  constexpr uint32_t ES = sizeof(CT);
+  if constexpr (ES == 4)
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), crow, c_off * ES, (uint32_t)(acc_row(r) * ldc) * ES + pcol, kCgStoreAux);
+  else
+    __builtin_amdgcn_raw_buffer_store_b16((uint16_t)__float_as_uint(v), crow, c_off * ES, (uint32_t)(acc_row(r) * ldc) * ES + pcol, kCgStoreAux);
 }
 // [r5] KS k-steps of 16: K = 16 KS in {64, 96, 128}.  The B slab of a 128-column group is 2 pieces x 128 columns x (32 KS + 16) bytes - 68 KB at
 // K = 128, 36 KB at K = 64, 52 KB at K = 96 - so the narrow forms keep THREE groups resident (G2 = 3: 108 / 156 KB).
@@ -400,12 +413,14 @@ __device__ __forceinline__ HFrag hg_frag(const unsigned char* sb, int ks) {
 // [r5] KS < 8: the zero-padded tall Linears of graph regression (50 + 1 -> 64 columns, 75 + 1 -> 96) no longer multiply, load, split and
 // write pad columns up to 128: at C2L the edge-feature product (4e5 x 51 -> 380) read its 205 MB padded operand three times (G2 = 1, 384 = 3
 // groups) for 614 MB of output; K = 64 with G2 = 3 reads 102 MB once.
-template <int G2, int KS = 8>
+template <int G2, int KS = 8, class CT = float>
 __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_kernel(const GemmParams p, const float* col_unscale, int64_t n_units,
                                                                            int n_groups, float* a_row_max) {
   constexpr int dbg = kAbl;
   using Geo = HgGeom<KS>;
   constexpr int K = 16 * KS;
+  constexpr int ES = sizeof(CT);                                       // bytes per element of C (p.C is a CT*: GemmParams keeps one layout)
+  CT* const Cp = reinterpret_cast<CT*>(p.C);
   __shared__ __attribute__((aligned(16))) unsigned char lds[G2 * Geo::group];
   constexpr int NT = 4 * G2;                                           // 32-column tiles per workgroup
   const int tid = threadIdx.x;
@@ -438,7 +453,7 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_kernel(cons
   float prev[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) prev[r] = 0.f;
-  __amdgpu_buffer_rsrc_t crow_p = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, 0, 0x00020000);
+  __amdgpu_buffer_rsrc_t crow_p = __builtin_amdgcn_make_buffer_rsrc(Cp, 0, 0, 0x00020000);
   uint32_t pcol = 0;
   // The rows of a unit are requested at the START of their own unit.  vmcnt is one in-order counter for loads and stores, so waiting for
   // them also waits for every store the wave issued before them (measurement builds, C4: 1.04 ms with the loads, 0.81 without, 0.75 for
@@ -489,7 +504,7 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_kernel(cons
       }
     }
     const __amdgpu_buffer_rsrc_t crow =
-        __builtin_amdgcn_make_buffer_rsrc(p.C + row0 * p.ldc, 0, (int)min((int64_t)0x7fffffff, rows_here * p.ldc * 4), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(Cp + row0 * p.ldc, 0, (int)min((int64_t)0x7fffffff, rows_here * p.ldc * ES), 0x00020000);
 #pragma unroll 1
     for (int ct = 0; ct < NT; ++ct) {
       int cue = cues[0];
@@ -529,7 +544,7 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_kernel(cons
 #pragma unroll
           for (int j = 0; j < SPK; ++j) {
             const int r = SPK * ks + j;
-            if (r < 16) cg_store(prev[r], crow_p, c_off, r, (int)p.ldc, pcol);
+            if (r < 16) cg_store<CT>(prev[r], crow_p, c_off, r, (int)p.ldc, pcol);
           }
         } else {
           asm volatile("" :: "v"(prev[(2 * ks) & 15]), "v"(prev[(2 * ks + 1) & 15]));
@@ -538,14 +553,14 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_kernel(cons
       }
       // row acc_row(r) + 4h of the tile: its scale lives in the lane with that r31
 #pragma unroll
-      for (int r = 0; r < 16; ++r) prev[r] = ldexpf(acc[r] + acl[r] * (1.f / 2048.f), cue - rse[r]);
+      for (int r = 0; r < 16; ++r) prev[r] = cg_out<CT>(ldexpf(acc[r] + acl[r] * (1.f / 2048.f), cue - rse[r]));
       crow_p = crow;
-      pcol = (uint32_t)(g * 32 * NT + ct * 32) * 4u;
+      pcol = (uint32_t)(g * 32 * NT + ct * 32) * ES;
     }
   }
   // the last tile of the last unit
 #pragma unroll
-  for (int r = 0; r < 16; ++r) cg_store(prev[r], crow_p, c_off, r, (int)p.ldc, pcol);
+  for (int r = 0; r < 16; ++r) cg_store<CT>(prev[r], crow_p, c_off, r, (int)p.ldc, pcol);
 }
 
 // ---- K == 256, three products (round 2, late): the forward [P|Q] = x [Wtop|Wbot] of hidden width 256 (C5) -----------------------------
@@ -562,9 +577,11 @@ constexpr int kH2Pitch = 256 * 2 + 16, kH2Piece = 32 * kH2Pitch, kH2Tile = 2 * k
 // pointers) so that each form keeps the kernel arguments it had.
 template <class T, class... R> __device__ __forceinline__ T arg0(T t, R...) { return t; }
 template <class T, class U> __device__ __forceinline__ U arg1(T, U u) { return u; }
-template <bool PACKED, class... A>
+template <bool PACKED, class CT, class... A>
 __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_k256_kernel(const GemmParams p, A... a_operand, const float* col_unscale,
                                                                                 int64_t n_units, int n_groups) {
+  constexpr int ES = sizeof(CT);                                       // bytes per element of C (p.C is a CT*)
+  CT* const Cp = reinterpret_cast<CT*>(p.C);
   __shared__ __attribute__((aligned(16))) unsigned char lds[kH2Lds];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -589,7 +606,7 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_k256_kernel
   float prev[16];                                  // the finished tile whose stores ride between the next tile's MFMAs (zero-byte descriptor at first)
 #pragma unroll
   for (int r = 0; r < 16; ++r) prev[r] = 0.f;
-  __amdgpu_buffer_rsrc_t crow_p = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, 0, 0x00020000);
+  __amdgpu_buffer_rsrc_t crow_p = __builtin_amdgcn_make_buffer_rsrc(Cp, 0, 0, 0x00020000);
   uint32_t pcol = 0;
   // [r5, measured and NOT kept] (packed form) the next unit's fragments requested during the last tile of this one, each k-step's two pieces
   // right behind the last MFMAs that read them (clean code: 192 MFMAs, four vmcnt waits per unit, no copies): 7.10 ms against 6.89 with the
@@ -650,7 +667,7 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_k256_kernel
       }
     }
     const __amdgpu_buffer_rsrc_t crow =
-        __builtin_amdgcn_make_buffer_rsrc(p.C + row0 * p.ldc, 0, (int)min((int64_t)0x7fffffff, rows_here * p.ldc * 4), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(Cp + row0 * p.ldc, 0, (int)min((int64_t)0x7fffffff, rows_here * p.ldc * ES), 0x00020000);
 #pragma unroll 1
     for (int ct = 0; ct < 4; ++ct) {
       int cue = cues[0];
@@ -682,20 +699,20 @@ __global__ __launch_bounds__(kCgThreads, 1) void gemm_f16x2_colgroup_k256_kernel
         // [r4] one store of the PREVIOUS tile behind every k-step (see gemm_f16x2_colgroup_kernel): the 17 GB this product writes at
         // hidden width 256 leave in a steady stream beside the MFMAs instead of in bursts between them
         if (!(kAbl & 4))
-          cg_store(prev[ks], crow_p, c_off, ks, (int)p.ldc, pcol);
+          cg_store<CT>(prev[ks], crow_p, c_off, ks, (int)p.ldc, pcol);
         else
           asm volatile("" :: "v"(prev[ks]));
         __builtin_amdgcn_sched_barrier(0);
         cur = nxt;
       }
 #pragma unroll
-      for (int r = 0; r < 16; ++r) prev[r] = ldexpf(acc[r] + acl[r] * (1.f / 2048.f), cue - rse[r]);
+      for (int r = 0; r < 16; ++r) prev[r] = cg_out<CT>(ldexpf(acc[r] + acl[r] * (1.f / 2048.f), cue - rse[r]));
       crow_p = crow;
-      pcol = (uint32_t)(g * 128 + ct * 32) * 4u;
+      pcol = (uint32_t)(g * 128 + ct * 32) * ES;
     }
   }
 #pragma unroll
-  for (int r = 0; r < 16; ++r) cg_store(prev[r], crow_p, c_off, r, (int)p.ldc, pcol);      // the last tile of the last unit
+  for (int r = 0; r < 16; ++r) cg_store<CT>(prev[r], crow_p, c_off, r, (int)p.ldc, pcol);      // the last tile of the last unit
 }
 
 // ---- [r5] K == 256 with a PACKED A operand ------------------------------------------------------------------------------------------
@@ -1987,51 +2004,97 @@ extern "C" int mma_split_f16x2(const float* w, int64_t stride_k, int64_t stride_
   return check_launch("split_f16x2_kernel");
 }
 
-extern "C" int mma_gemm_f16x2(const float* A, int64_t lda, const void* Bt2, const float* col_unscale, float* C, int64_t ldc,
-                              float* a_row_max, int64_t M, int32_t N, void* stream) {
+// ---- the column-group three-product forms, for both output types: CT = float, or uint16_t = bf16 written from the epilogue (ABI 39, the
+// `_h` entry points).  One set of checks and one launch ladder per form; ldc counts elements of C.  The bf16 kernels store single 2-byte
+// elements, so a bf16 C needs 2-byte alignment only and any ldc >= N; an odd address is refused with the other pointers.
+template <class CT> static bool c_ok(const CT* C) { return C && (reinterpret_cast<uintptr_t>(C) & (sizeof(CT) - 1)) == 0; }
+template <class CT> static GemmParams cg_params(const float* A, int64_t lda, const void* Bt2, CT* C, int64_t ldc, int64_t M, int N, int K) {
+  return GemmParams{A, lda, static_cast<const __bf16*>(Bt2), reinterpret_cast<float*>(C), ldc, M, N, K, 0};      // the kernel reads C as CT*
+}
+
+template <class CT>
+static int gemm_f16x2_k128(const float* A, int64_t lda, const void* Bt2, const float* col_unscale, CT* C, int64_t ldc, float* a_row_max,
+                           int64_t M, int32_t N, void* stream) {
   MMA_CHECKED(colgroup_shape(M, N));
-  MMA_CHECKED(nn_operands(A, lda, 128, Bt2, col_unscale && C, ldc, N, M));
-  GemmParams p{A, lda, static_cast<const __bf16*>(Bt2), C, ldc, M, N, 128, 0};
+  MMA_CHECKED(nn_operands(A, lda, 128, Bt2, col_unscale && c_ok(C), ldc, N, M));
+  const GemmParams p = cg_params(A, lda, Bt2, C, ldc, M, N, 128);
   const int64_t n_units = (M + kCgRows - 1) / kCgRows;
   const int groups = N / 128;
   if (groups % 2 == 0)        // pairs of column groups per workgroup
-    hipLaunchKernelGGL(gemm_f16x2_colgroup_kernel<2>, dim3(256), dim3(kCgThreads), 0, static_cast<hipStream_t>(stream), p, col_unscale,
+    hipLaunchKernelGGL((gemm_f16x2_colgroup_kernel<2, 8, CT>), dim3(256), dim3(kCgThreads), 0, static_cast<hipStream_t>(stream), p, col_unscale,
                        n_units, groups / 2, a_row_max);
   else
-    hipLaunchKernelGGL(gemm_f16x2_colgroup_kernel<1>, dim3(256), dim3(kCgThreads), 0, static_cast<hipStream_t>(stream), p, col_unscale,
+    hipLaunchKernelGGL((gemm_f16x2_colgroup_kernel<1, 8, CT>), dim3(256), dim3(kCgThreads), 0, static_cast<hipStream_t>(stream), p, col_unscale,
                        n_units, groups, a_row_max);
   return check_launch("gemm_f16x2_colgroup_kernel");
 }
 
 // [r5] K in {64, 96}: the narrow forms of the column-group kernel (Bt2 (2, N, K)); three resident groups where N / 128 is a multiple of 3
-extern "C" int mma_gemm_f16x2_k(const float* A, int64_t lda, const void* Bt2, const float* col_unscale, float* C, int64_t ldc,
-                                float* a_row_max, int64_t M, int32_t N, int32_t K, void* stream) {
-  if (K == 128) return mma_gemm_f16x2(A, lda, Bt2, col_unscale, C, ldc, a_row_max, M, N, stream);
+template <class CT>
+static int gemm_f16x2_k(const float* A, int64_t lda, const void* Bt2, const float* col_unscale, CT* C, int64_t ldc, float* a_row_max,
+                        int64_t M, int32_t N, int32_t K, void* stream) {
+  if (K == 128) return gemm_f16x2_k128<CT>(A, lda, Bt2, col_unscale, C, ldc, a_row_max, M, N, stream);
   MMA_REQUIRE(K == 64 || K == 96, "K=%d unsupported (64, 96 or 128)", K);
   MMA_CHECKED(colgroup_shape(M, N));
-  MMA_CHECKED(nn_operands(A, lda, K, Bt2, col_unscale && C, ldc, N, M));
-  GemmParams p{A, lda, static_cast<const __bf16*>(Bt2), C, ldc, M, N, K, 0};
+  MMA_CHECKED(nn_operands(A, lda, K, Bt2, col_unscale && c_ok(C), ldc, N, M));
+  const GemmParams p = cg_params(A, lda, Bt2, C, ldc, M, N, K);
   const int64_t n_units = (M + kCgRows - 1) / kCgRows;
   const int groups = N / 128;
   int g2 = groups % 3 == 0 ? 3 : (groups % 2 == 0 ? 2 : 1);
   { const char* e = getenv("MMA_F16X2_G2"); if (e && e[0] >= '1' && e[0] <= '3' && groups % (e[0] - '0') == 0) g2 = e[0] - '0'; }      // A/B, read per call
   hipStream_t st = static_cast<hipStream_t>(stream);
-#define MMA_CG(GG, KK) hipLaunchKernelGGL((gemm_f16x2_colgroup_kernel<GG, KK>), dim3(256), dim3(kCgThreads), 0, st, p, col_unscale, n_units, groups / GG, a_row_max)
+#define MMA_CG(GG, KK) hipLaunchKernelGGL((gemm_f16x2_colgroup_kernel<GG, KK, CT>), dim3(256), dim3(kCgThreads), 0, st, p, col_unscale, n_units, groups / GG, a_row_max)
   if (K == 64) { if (g2 == 3) MMA_CG(3, 4); else if (g2 == 2) MMA_CG(2, 4); else MMA_CG(1, 4); }
   else         { if (g2 == 3) MMA_CG(3, 6); else if (g2 == 2) MMA_CG(2, 6); else MMA_CG(1, 6); }
 #undef MMA_CG
   return check_launch("gemm_f16x2_colgroup_kernel (narrow)");
 }
 
-extern "C" int mma_gemm_f16x2_k256(const float* A, int64_t lda, const float* row_max, const void* Bt2, const float* col_unscale, float* C,
-                                   int64_t ldc, int64_t M, int32_t N, void* stream) {
+template <class CT>
+static int gemm_f16x2_k256(const float* A, int64_t lda, const float* row_max, const void* Bt2, const float* col_unscale, CT* C, int64_t ldc,
+                           int64_t M, int32_t N, void* stream) {
   MMA_CHECKED(colgroup_shape(M, N));
-  MMA_CHECKED(nn_operands(A, lda, 256, Bt2, row_max && col_unscale && C, ldc, N, M));
-  GemmParams p{A, lda, static_cast<const __bf16*>(Bt2), C, ldc, M, N, 256, 0};
+  MMA_CHECKED(nn_operands(A, lda, 256, Bt2, row_max && col_unscale && c_ok(C), ldc, N, M));
+  const GemmParams p = cg_params(A, lda, Bt2, C, ldc, M, N, 256);
   const int64_t n_units = (M + kCgRows - 1) / kCgRows;
-  hipLaunchKernelGGL((gemm_f16x2_colgroup_k256_kernel<false, const float*>), dim3(256), dim3(kCgThreads), 0, static_cast<hipStream_t>(stream), p, row_max, col_unscale,
+  hipLaunchKernelGGL((gemm_f16x2_colgroup_k256_kernel<false, CT, const float*>), dim3(256), dim3(kCgThreads), 0, static_cast<hipStream_t>(stream), p, row_max, col_unscale,
                      n_units, N / 128);
   return check_launch("gemm_f16x2_colgroup_k256_kernel");
+}
+
+template <class CT>
+static int gemm_f16x2_k256p(const void* Ap, const int32_t* sce, const void* Bt2, const float* col_unscale, CT* C, int64_t ldc, int64_t M,
+                            int32_t N, void* stream) {
+  MMA_CHECKED(colgroup_shape(M, N));
+  MMA_REQUIRE(ldc >= N && ldc < (1 << 24), "row pitch too small or >= 2^24");
+  if (M == 0) return 0;
+  MMA_CHECKED(nn_pointers(Ap, Bt2, sce && col_unscale && c_ok(C)));        // (no A pitch: the packed operand has its own layout)
+  const GemmParams p = cg_params<CT>(nullptr, 256, Bt2, C, ldc, M, N, 256);
+  const int64_t n_units = (M + kCgRows - 1) / kCgRows;
+  hipLaunchKernelGGL((gemm_f16x2_colgroup_k256_kernel<true, CT, const uint4* __restrict__, const int* __restrict__>), dim3(256), dim3(kCgThreads), 0, static_cast<hipStream_t>(stream), p,
+                     static_cast<const uint4*>(Ap), sce, col_unscale, n_units, N / 128);
+  return check_launch("gemm_f16x2_colgroup_k256_kernel (packed)");
+}
+
+extern "C" int mma_gemm_f16x2(const float* A, int64_t lda, const void* Bt2, const float* col_unscale, float* C, int64_t ldc,
+                              float* a_row_max, int64_t M, int32_t N, void* stream) {
+  return gemm_f16x2_k128<float>(A, lda, Bt2, col_unscale, C, ldc, a_row_max, M, N, stream);
+}
+extern "C" int mma_gemm_f16x2_k(const float* A, int64_t lda, const void* Bt2, const float* col_unscale, float* C, int64_t ldc,
+                                float* a_row_max, int64_t M, int32_t N, int32_t K, void* stream) {
+  return gemm_f16x2_k<float>(A, lda, Bt2, col_unscale, C, ldc, a_row_max, M, N, K, stream);
+}
+extern "C" int mma_gemm_f16x2_k_h(const float* A, int64_t lda, const void* Bt2, const float* col_unscale, uint16_t* C, int64_t ldc,
+                                  float* a_row_max, int64_t M, int32_t N, int32_t K, void* stream) {
+  return gemm_f16x2_k<uint16_t>(A, lda, Bt2, col_unscale, C, ldc, a_row_max, M, N, K, stream);
+}
+extern "C" int mma_gemm_f16x2_k256(const float* A, int64_t lda, const float* row_max, const void* Bt2, const float* col_unscale, float* C,
+                                   int64_t ldc, int64_t M, int32_t N, void* stream) {
+  return gemm_f16x2_k256<float>(A, lda, row_max, Bt2, col_unscale, C, ldc, M, N, stream);
+}
+extern "C" int mma_gemm_f16x2_k256_h(const float* A, int64_t lda, const float* row_max, const void* Bt2, const float* col_unscale, uint16_t* C,
+                                     int64_t ldc, int64_t M, int32_t N, void* stream) {
+  return gemm_f16x2_k256<uint16_t>(A, lda, row_max, Bt2, col_unscale, C, ldc, M, N, stream);
 }
 
 // [r5] the packed A operand of mma_gemm_f16x2_k256p: Ap = ceil(M / 32) units of 32 KB (mma_pack_f16x2_k256_bytes), sce (M,) int32 scale
@@ -2048,15 +2111,11 @@ extern "C" int mma_pack_f16x2_k256(const float* A, int64_t lda, int64_t M, void*
 }
 extern "C" int mma_gemm_f16x2_k256p(const void* Ap, const int32_t* sce, const void* Bt2, const float* col_unscale, float* C, int64_t ldc,
                                     int64_t M, int32_t N, void* stream) {
-  MMA_CHECKED(colgroup_shape(M, N));
-  MMA_REQUIRE(ldc >= N && ldc < (1 << 24), "row pitch too small or >= 2^24");
-  if (M == 0) return 0;
-  MMA_CHECKED(nn_pointers(Ap, Bt2, sce && col_unscale && C));        // (no A pitch: the packed operand has its own layout)
-  GemmParams p{nullptr, 256, static_cast<const __bf16*>(Bt2), C, ldc, M, N, 256, 0};
-  const int64_t n_units = (M + kCgRows - 1) / kCgRows;
-  hipLaunchKernelGGL((gemm_f16x2_colgroup_k256_kernel<true, const uint4* __restrict__, const int* __restrict__>), dim3(256), dim3(kCgThreads), 0, static_cast<hipStream_t>(stream), p,
-                     static_cast<const uint4*>(Ap), sce, col_unscale, n_units, N / 128);
-  return check_launch("gemm_f16x2_colgroup_k256_kernel (packed)");
+  return gemm_f16x2_k256p<float>(Ap, sce, Bt2, col_unscale, C, ldc, M, N, stream);
+}
+extern "C" int mma_gemm_f16x2_k256p_h(const void* Ap, const int32_t* sce, const void* Bt2, const float* col_unscale, uint16_t* C, int64_t ldc,
+                                      int64_t M, int32_t N, void* stream) {
+  return gemm_f16x2_k256p<uint16_t>(Ap, sce, Bt2, col_unscale, C, ldc, M, N, stream);
 }
 
 extern "C" int mma_gemm_f16x2_n128(const float* A, int64_t lda, const float* row_max, const void* Bt2, const float* col_unscale, float* C,

@@ -209,16 +209,11 @@ extern "C" int mma_edge_fold_bwd(const float* We, int64_t ldw, const float* Wenc
 
 // ---- fp32 rows -> bf16 rows: the logit tables [P | Q] of the NC layer's bf16 form (mma_nc_fused_fwd_h / _bwd_h), converted ONCE per
 // call from the forward GEMM's (N, 2*K*H) output - N rows, against the E per-edge gathers that then read half the bytes.  Round to
-// nearest even on the bit pattern; inf stays inf, a NaN becomes the quiet NaN 0x7FC0 (what torch's fp32 -> bfloat16 conversion gives).
+// nearest even on the bit pattern; inf stays inf, a NaN becomes the quiet NaN 0x7FC0 (what torch's fp32 -> bfloat16 conversion gives):
+// bf16_rne of common.h, the rounding the bf16-output GEMMs (mma_gemm_f16x2_*_h) apply in their epilogue.
 namespace mma {
 
 typedef uint32_t mma_pack_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t bf16_rne(float f) {
-  const uint32_t b = __float_as_uint(f);
-  if ((b & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;
-  return (b + 0x7FFFu + ((b >> 16) & 1u)) >> 16;       // a carry out of the mantissa moves into the exponent (up to inf), as it must
-}
-
 template <bool V4>
 __global__ __launch_bounds__(kBlock) void rows_to_bf16_kernel(const float* __restrict__ src, int64_t lds, uint16_t* __restrict__ dst, int64_t ldd,
                                                               int64_t rows, int64_t cols) {

@@ -30,6 +30,9 @@ F16X2_K = (64, 96, 128)      # reduction widths of the whole-row three-product k
 PACK_K256 = flag("MMA_PACK_K256")     # 0: round 4's K = 256 forward (fp32 rows split per column group)
 USE_NLP = flag("MMA_DX_NLP")          # round 4: the pipelined one-accumulator form (0: round 3's kernel)
 TN_KA256 = flag("MMA_TN_KA256")       # 0: 128-column blocks of x, one launch each (round 3)
+BF16_EPILOGUE = flag("MMA_BF16_EPILOGUE")      # a bf16 `out` of mm_into is written by the GEMM's own epilogue where the form has one (0: fp32
+                                               # product + the mma_rows_to_bf16 pass everywhere)
+_BF16_OUT_FORMS = ("f16x2_k", "f16x2_k256", "f16x2_k256p")      # the forms with a bf16-output twin (the `_h` entry points, ABI 39)
 
 
 # ---- shape -> form: pure functions of integers and of the switches above, which they read when called (bench.py and the tests set them)
@@ -104,9 +107,17 @@ def _gpu_f32(*ts, unit_cols=False, aligned=False):
 
 
 # ---- form -> runner: (a, w, out, accumulate, row_max, box) with `out` allocated; each states its span name and mfma kind ------------
-def _gemm_span(name, mfma, M, K, N, accumulate=False):
-    """A in once (algorithmic: column blocks re-read it; B is 0.5 MB), C out - and in, when accumulating.  TN: x and g in once."""
-    return _span(name, nbytes=4 * M * (K + (2 if accumulate else 1) * N), flops=2 * M * K * N, mfma=mfma)
+def _gemm_span(name, mfma, M, K, N, accumulate=False, c_bytes=4):
+    """A in once (algorithmic: column blocks re-read it; B is 0.5 MB), C out - and in, when accumulating.  TN: x and g in once.
+    c_bytes: 2 for a bf16 C."""
+    return _span(name, nbytes=M * (4 * K + c_bytes * (2 if accumulate else 1) * N), flops=2 * M * K * N, mfma=mfma)
+
+
+def _c_suffix(out):
+    """"" / "_h": the entry point for the dtype of C, and the size of its elements."""
+    if out.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("the three-product column-group GEMMs write float32 or bfloat16, but got %r" % (out.dtype,))
+    return ("", 4) if out.dtype == torch.float32 else ("_h", 2)
 
 
 def _row_max(a, box, fill=True):
@@ -138,23 +149,28 @@ def _split_f16x2(w, plain_lo=False):
     return bt2, cu
 
 
-def gemm_f16x2(a, w, out=None, row_max_out=None):
+def gemm_f16x2(a, w, out=None, row_max_out=None, out_dtype=torch.float32):
     """a (M,K) @ w (K,N), K in F16X2_K, N % 128 == 0: the three-product form (fp16 hi/lo pieces, power-of-two row and column scales).
-    row_max_out (M,): the kernel also leaves max |a[i,:]| there (it forms them for its row scales anyway)."""
+    row_max_out (M,): the kernel also leaves max |a[i,:]| there (it forms them for its row scales anyway).
+    out_dtype torch.bfloat16 (or a bf16 `out`, whose dtype decides): the kernel's epilogue rounds its fp32 result to nearest even and
+    stores bf16 (mma_gemm_f16x2_k_h) - the bits mma_rows_to_bf16 makes of the fp32 call's result, without that buffer or pass."""
     (M, K), N = a.shape, w.shape[1]
-    bt2, cu = _split_f16x2(w)
     if out is None:
-        out = torch.empty((M, N), device=a.device, dtype=torch.float32)
-    with _gemm_span("gemm_x3_k128", "f16x3", M, K, N):
-        call("mma_gemm_f16x2_k", ptr(a), a.stride(0), ptr(bt2), ptr(cu), ptr(out), out.stride(0), ptr(row_max_out), M, N, K, stream_ptr())
+        out = torch.empty((M, N), device=a.device, dtype=out_dtype)
+    h, c_bytes = _c_suffix(out)
+    bt2, cu = _split_f16x2(w)
+    with _gemm_span("gemm_x3_k128", "f16x3", M, K, N, c_bytes=c_bytes):
+        call("mma_gemm_f16x2_k" + h, ptr(a), a.stride(0), ptr(bt2), ptr(cu), ptr(out), out.stride(0), ptr(row_max_out), M, N, K, stream_ptr())
     return out
 
 
 def _run_f16x2_k256(a, w, out, accumulate, rm, box, packed=False):
     """K = 256 (C5 forward, N = 4096) with the whole 256-deep B slab resident per column group: A is read once per group through L2,
     not once per 128-column launch from HBM.  packed [r5]: A goes into fp16 fragment order first (one pass: row maxima, scale
-    exponents, both pieces) and the 32 column groups stop re-splitting its rows; else the row maxima take a pass."""
+    exponents, both pieces) and the 32 column groups stop re-splitting its rows; else the row maxima take a pass.
+    A bf16 `out` is written by the kernel's epilogue (the `_h` entry points), as in gemm_f16x2."""
     (M, K), N = a.shape, w.shape[1]
+    h, c_bytes = _c_suffix(out)
     rm = _row_max(a, box, fill=not packed)
     bt2, cu = _split_f16x2(w)
     if packed:
@@ -163,8 +179,8 @@ def _run_f16x2_k256(a, w, out, accumulate, rm, box, packed=False):
         with _span("pack_f16x2", nbytes=8 * M * K, flops=0):
             call("mma_pack_f16x2_k256", ptr(a), a.stride(0), M, ptr(ap), ptr(sce), ptr(rm), stream_ptr())
     rows = (ptr(ap), ptr(sce)) if packed else (ptr(a), a.stride(0), ptr(rm))
-    with _gemm_span("gemm_x3_persist", "f16x3", M, K, N):
-        call("mma_gemm_f16x2_k256p" if packed else "mma_gemm_f16x2_k256", *rows, ptr(bt2), ptr(cu), ptr(out), out.stride(0), M, N, stream_ptr())
+    with _gemm_span("gemm_x3_persist", "f16x3", M, K, N, c_bytes=c_bytes):
+        call(("mma_gemm_f16x2_k256p" if packed else "mma_gemm_f16x2_k256") + h, *rows, ptr(bt2), ptr(cu), ptr(out), out.stride(0), M, N, stream_ptr())
     return out
 
 
@@ -232,14 +248,26 @@ def _nn(a, w, out=None, accumulate=False, row_max=None, box=None, named=False):
     if M == 0 and out is not None:
         return out
     aligned = _gpu_f32(a, aligned=True)
+    # a bf16 `out` (mm_into): the form is the one an fp32 `out` of the same shape takes
+    out_h = out is not None and out.dtype == torch.bfloat16
+    assert not (out_h and (accumulate or not out.is_cuda or out.shape != (M, N) or out.stride(1) != 1)), "a bf16 out: a GPU (M, N) matrix, never accumulated into"
     form = "lib" if not (named or _gpu_f32(a, w)) else nn_form(
         M, a.shape[1], N, accumulate=accumulate, row_max_known=row_max is not None,
-        out_ok=out is None or _gpu_f32(out, unit_cols=True), aligned=aligned, named=named)
+        out_ok=out is None or out_h or _gpu_f32(out, unit_cols=True), aligned=aligned, named=named)
+    dst = None
+    if out_h and not (BF16_EPILOGUE and form in _BF16_OUT_FORMS):
+        # no bf16 epilogue on this form (or the switch is off): the fp32 product as for an fp32 `out`, then the conversion pass - the
+        # same function of the inputs on every shape
+        dst, out = out, torch.empty((M, N), device=out.device, dtype=torch.float32)
     if form != "lib":
         a = a if aligned else a.contiguous()
-        assert not accumulate if out is None else (out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.float32)
+        assert not accumulate if out is None else (out.shape == (M, N) and out.stride(1) == 1 and out.dtype in (torch.float32, torch.bfloat16))
         out = out if out is not None else torch.empty((M, N), device=a.device, dtype=torch.float32)
-    return _NN_RUN[form](a, w, out, accumulate, row_max, box)
+    res = _NN_RUN[form](a, w, out, accumulate, row_max, box)
+    if dst is None:
+        return res
+    from . import functional as Fn      # late: functional imports this module
+    return Fn.rows_to_bf16(res, dst)
 
 
 def gemm_bf16x3(a, w, out=None, accumulate=False, row_max_box=None):
@@ -257,7 +285,10 @@ def gemm_f16x2_n128(a, row_max, w, out, accumulate=False):
 
 def mm_into(a, w, out, row_max_box=None):
     """out[...] = a @ w (no autograd): the forward GEMMs of the sharded layer write row blocks of one buffer.  row_max_box: see
-    gemm_bf16x3 (stays empty when the path taken does not form the row maxima of a)."""
+    gemm_bf16x3 (stays empty when the path taken does not form the row maxima of a).
+    out may be bf16 (the logit tables of MMA(..., logit_dtype=torch.bfloat16)): the form is the one nn_form picks for an fp32 out of the
+    same shape; on f16x2_k / f16x2_k256 / f16x2_k256p the kernel rounds and writes bf16 from its epilogue (BF16_EPILOGUE), on every
+    other form the product goes to an fp32 temporary and rows_to_bf16 converts it - the same bits either way."""
     return _nn(a, w, out, box=row_max_box)
 
 
@@ -296,8 +327,9 @@ def _run_tn(form, x, g, x_row_max=None, g_row_max=None):
     ws = torch.empty((n_ws,), device=x.device, dtype=torch.float32) if n_ws else None
     with _gemm_span("gemm_x3_tn", "f16x3" if f16 else "bf16x6", N, KA, NC):
         for j in range(0, KA, kb):       # one launch per column block of x (= row block of the result); the maxima of the whole row bound every block's
+            # (the last block may be narrower - KA = 200 is 128 + 72: its launch is told so, it must not write kb rows into the 72 `out` has left)
             call("mma_gemm_" + form, ptr(x[:, j:j + kb]), x.stride(0), ptr(g), g.stride(0), *((ptr(x_row_max), ptr(g_row_max)) if f16 else ()),
-                 ptr(out[j:j + kb]), ptr(ws), n_ws, N, kb, NC, stream_ptr())
+                 ptr(out[j:j + kb]), ptr(ws), n_ws, N, min(kb, KA - j), NC, stream_ptr())
     return out
 
 

@@ -256,14 +256,14 @@ class _NCLocalLayer(torch.autograd.Function):
         N, H = x.shape
         K = len(kinds)
         KH = K * H
-        PQ = torch.empty((N, 2 * KH), device=x.device, dtype=torch.float32)
+        # bf16 logit tables: the forward GEMM itself leaves [P | Q] in bf16 (its epilogue rounds; forms without one convert an fp32
+        # temporary - dense.mm_into), so K1 and K2b gather - and the backward keeps - tables of half the size
+        PQ = torch.empty((N, 2 * KH), device=x.device, dtype=check_logit_dtype(logit_dtype))
         ctx.cat_given = wbot is None                                        # wtop IS [Wtop | Wbot] (H, 2*K*H): mask_weights()
         wcat = wtop if ctx.cat_given else torch.cat([wtop, wbot], 1)        # (H, 2*K*H)
         need = any(ctx.needs_input_grad[:3])
         box = [] if need else None                                          # row maxima of x, when the forward GEMM forms them: the
         mm_into(x, wcat, PQ, row_max_box=box)                               # weight-gradient product's row scales (three-product TN form)
-        if check_logit_dtype(logit_dtype) == torch.bfloat16:
-            PQ = rows_to_bf16(PQ)       # N rows converted once; K1 and K2b gather (and the backward keeps) the half-size tables
         msum, T, sel, crow = nc_fwd_launch(x, PQ[:, :KH], PQ[:, KH:], graph, kinds, acts, drop, True, need)
         ctx.graph, ctx.kinds, ctx.acts, ctx.drop = graph, kinds, acts, drop
         ctx.save_for_backward(x, PQ, T, sel, crow, wcat, box[0] if box else None)
@@ -295,8 +295,8 @@ class _NCLocalLayer(torch.autograd.Function):
 def nc_local_layer(x, wtop, wbot, graph, kinds, acts, drop=None, logit_dtype=torch.float32):
     """sum_k m_k (graph.N, H) straight from the features and the concatenated mask weights (unsharded graphs).
     wbot=None: `wtop` is already [Wtop | Wbot] (H, 2*K*H), e.g. from mask_weights().
-    logit_dtype=torch.bfloat16: the [P | Q] buffer of the forward GEMM is rounded to bf16 once (mma_rows_to_bf16) and the bf16 buffer
-    is what the fused kernels gather and what is saved for the backward (half the saved activation); every sum, x and every gradient
+    logit_dtype=torch.bfloat16: the forward GEMM writes [P | Q] rounded to bf16 (from its own epilogue on the column-group forms, else
+    through mma_rows_to_bf16: dense.mm_into) and the bf16 buffer is what the fused kernels gather and what is saved for the backward (half the saved activation); every sum, x and every gradient
     stay fp32, and the gradients are the exact ones of the function evaluated on the rounded logits."""
     check_logit_dtype(logit_dtype)
     assert graph.n_src == graph.N

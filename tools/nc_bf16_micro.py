@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """The MMA layer with fp32 and with bf16 logit tables (MMA(..., logit_dtype=)) on bench.py's C4-shape synthetic graph (R-MAT scale 20,
-5 M undirected edges, H = 128, sum / mean / max / min, hash dropout 0.5), both in ONE process, interleaved rounds after a warm-up:
-  * the layer's forward + backward step, HIP events around `--steps` steps per round (bench.py's default step count or more);
-  * the two fused calls on their own (K1: mma_nc_fused_fwd[_h]; K2b with the node-level epilogue: mma_nc_fused_bwd[_h]) on prepared
-    tables, events around `--reps` back-to-back calls;
-  * the conversion launch (mma_rows_to_bf16 of the (N, 2*K*H) forward GEMM output) the bf16 step pays.
-Prints one JSON line: median ms of each, the bf16 / fp32 ratios and the device name.
+5 M undirected edges, H = 128, sum / mean / max / min, hash dropout 0.5).  THREE forms in ONE process, interleaved rounds after a warm-up:
+fp32 tables; bf16 tables through the conversion pass (dense.BF16_EPILOGUE = False: fp32 forward GEMM + mma_rows_to_bf16); bf16 tables
+written by the forward GEMM's epilogue (the default).
+  * the layer's forward + backward step of each form, HIP events around `--steps` steps per round (bench.py's default step count or more);
+  * the forward GEMM [P|Q] = x [Wtop|Wbot] alone, fp32-out and bf16-out (dense.mm_into), events around `--reps` back-to-back calls;
+  * the conversion launch (mma_rows_to_bf16 of the (N, 2*K*H) fp32 output) the conversion form pays;
+  * the two fused calls on their own (K1: mma_nc_fused_fwd[_h]; K2b with the node-level epilogue: mma_nc_fused_bwd[_h]) on prepared tables.
+Prints one JSON line: median and [min, max] ms of each, the ratios and the device name.
 
     python tools/nc_bf16_micro.py [--rounds 5] [--steps 10] [--reps 10] [--scale 20 --edges 5000000 --hidden 128]   (on the GPU box)"""
 import argparse
@@ -20,6 +22,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mma_amd  # noqa: E402
 from bench import C4_DEFAULTS, make_layer  # noqa: E402
+from mma_amd import dense  # noqa: E402
 from mma_amd import functional as Fn  # noqa: E402
 from tools.synth import feature_rows, rmat_graph  # noqa: E402
 
@@ -65,8 +68,9 @@ def timed(fn, n):
     return start.elapsed_time(end) / n
 
 
-def layer_step(layer):
+def layer_step(layer, epilogue=True):
     def step():
+        dense.BF16_EPILOGUE = epilogue
         x.grad = None
         for prm in layer.owned:
             prm.grad = None
@@ -102,9 +106,24 @@ def bwd(tag):
     return run
 
 
-work = {}
+# the forward GEMM alone: the same operands into an fp32 and into a bf16 [P|Q] (the epilogue form)
+wcat = Fn.mask_weights([getattr(layers["fp32"], "mask_" + n).detach() for n in names])
+gemm_out = {"fp32": torch.empty((N, 2 * KH), device=dev), "bf16": torch.empty((N, 2 * KH), device=dev, dtype=torch.bfloat16)}
+gemm_form = dense.nn_form(N, H, 2 * KH)
+
+
+def gemm(tag):
+    def run():
+        dense.BF16_EPILOGUE = True
+        dense.mm_into(x.detach(), wcat, gemm_out[tag])
+    return run
+
+
+work = {"step_fp32": (layer_step(layers["fp32"]), args.steps),
+        "step_bf16_conversion": (layer_step(layers["bf16"], epilogue=False), args.steps),
+        "step_bf16_epilogue": (layer_step(layers["bf16"], epilogue=True), args.steps)}
 for tag in ("fp32", "bf16"):
-    work["step_" + tag] = (layer_step(layers[tag]), args.steps)
+    work["gemm_fwd_" + tag + "_out"] = (gemm(tag), args.reps)
     work["nc_fused_fwd_" + tag] = (fwd(tag), args.reps)
     work["nc_fused_bwd_" + tag] = (bwd(tag), args.reps)
 work["rows_to_bf16"] = (lambda: Fn.rows_to_bf16(PQ32, tables["bf16"]), args.reps)
@@ -121,5 +140,11 @@ med = {name: statistics.median(v) for name, v in ms.items()}
 out = {"device": torch.cuda.get_device_name(0), "N": N, "E": E, "H": H, "K": K, "dropout": args.dropout, "rounds": args.rounds,
        "steps": args.steps, "reps": args.reps, "median_ms": {k: round(v, 4) for k, v in med.items()},
        "min_max_ms": {k: [round(min(v), 4), round(max(v), 4)] for k, v in ms.items()},
-       "bf16_over_fp32": {k: round(med[k + "_bf16"] / med[k + "_fp32"], 4) for k in ("step", "nc_fused_fwd", "nc_fused_bwd")}}
+       "forward_gemm_form": gemm_form,
+       "bf16_over_fp32": dict({k: round(med[k + "_bf16"] / med[k + "_fp32"], 4) for k in ("nc_fused_fwd", "nc_fused_bwd")},
+                              gemm_fwd=round(med["gemm_fwd_bf16_out"] / med["gemm_fwd_fp32_out"], 4),
+                              step_conversion=round(med["step_bf16_conversion"] / med["step_fp32"], 4),
+                              step_epilogue=round(med["step_bf16_epilogue"] / med["step_fp32"], 4)),
+       "epilogue_over_conversion_step": round(med["step_bf16_epilogue"] / med["step_bf16_conversion"], 4)}
+dense.BF16_EPILOGUE = True
 print(json.dumps(out))
