@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MMA_ABI_VERSION 39
+#define MMA_ABI_VERSION 40
 #define MMA_MAX_K 8          /* masks fused per launch; more are issued as several launches */
 
 /* combine kinds of the node-classification aggregators (layers.py:201-728) */
@@ -224,6 +224,31 @@ int mma_nc_std_bwd(
     const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
     float* partial, int64_t n_slots,
     float* gQ, int64_t ldgq, float* gx, int64_t ldgx,
+    int64_t N, int64_t E, int32_t H, const uint8_t* act_host,
+    int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
+    void* stream);
+
+/* ABI 40: bf16 logit tables for the std kernels.  mma_nc_std_fwd_h / mma_nc_std_bwd_h: the same kernels, arguments, checks and results
+ * as mma_nc_std_fwd / mma_nc_std_bwd, with P and Q held as bf16 (uint16_t bit patterns, pitches ldp / ldq in ELEMENTS), as
+ * mma_nc_fused_fwd_h / mma_nc_fused_bwd_h hold theirs: only the four table loads change (the forward's own P row and gathered Q rows,
+ * the backward's own Q row and gathered P rows), a value is widened with bits << 16 (exact), and the backward recomputes z from what the
+ * forward read.  A table row is read as 8-byte vectors when H % 4 == 0, ldp % 4 == 0, ldq % 4 == 0 and both tables are 8-byte aligned,
+ * else as scalar 2-byte loads; a table at an odd address is refused.  x, saved, partial, g, gr, gP, gQ, gx keep their types; gP / gQ are
+ * the gradients with respect to the STORED table values (straight-through). */
+int mma_nc_std_fwd_h(
+    const float* x, int64_t ldx, const uint16_t* P, int64_t ldp, const uint16_t* Q, int64_t ldq,
+    const int32_t* rowptr, const int32_t* col,
+    const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
+    double* partial, int64_t n_slots, float* m, int64_t ldms, float* saved, int64_t ldt,
+    int64_t N, int64_t E, int32_t H, const uint8_t* act_host,
+    int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
+    void* stream);
+int mma_nc_std_bwd_h(
+    const float* x, int64_t ldx, const uint16_t* P, int64_t ldp, const uint16_t* Q, int64_t ldq,
+    const float* g, int64_t ldg, const float* saved, int64_t ldt, float* gr, int64_t ldgr, float* gP, int64_t ldgp, int64_t n_targets,
+    const int32_t* t_col, const int32_t* t_eid,
+    const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
+    float* partial, int64_t n_slots, float* gQ, int64_t ldgq, float* gx, int64_t ldgx,
     int64_t N, int64_t E, int32_t H, const uint8_t* act_host,
     int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
     void* stream);

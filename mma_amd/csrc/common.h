@@ -58,6 +58,34 @@ template <> __device__ __forceinline__ Vec<4> ldv_nt<4>(const float* p) {
 }
 template <> __device__ __forceinline__ Vec<1> ldv_nt<1>(const float* p) { Vec<1> r; r.v[0] = __builtin_nontemporal_load(p); return r; }
 
+// a row of a logit table held as TT = float, or as bf16 in uint16_t (the `_h` entry points of the NC and std kernels): 4 columns per
+// lane as ONE 8-byte load (VEC = 4) or scalar 2-byte loads (VEC = 1), widened with bits << 16, which is exact
+typedef uint32_t mma_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ Vec<4> widen_bf16x4(uint32_t lo, uint32_t hi) {
+  Vec<4> r;
+  r.v[0] = __uint_as_float(lo << 16); r.v[1] = __uint_as_float(lo & 0xFFFF0000u);
+  r.v[2] = __uint_as_float(hi << 16); r.v[3] = __uint_as_float(hi & 0xFFFF0000u);
+  return r;
+}
+template <int VEC> __device__ __forceinline__ Vec<VEC> ldt(const float* p) { return ldv<VEC>(p); }
+template <int VEC> __device__ __forceinline__ Vec<VEC> ldt_nt(const float* p) { return ldv_nt<VEC>(p); }
+template <int VEC> __device__ __forceinline__ Vec<VEC> ldt(const uint16_t* p) {
+  if constexpr (VEC == 4) {
+    const uint2 t = *reinterpret_cast<const uint2*>(p);
+    return widen_bf16x4(t.x, t.y);
+  } else {
+    Vec<1> r; r.v[0] = __uint_as_float((uint32_t)*p << 16); return r;
+  }
+}
+template <int VEC> __device__ __forceinline__ Vec<VEC> ldt_nt(const uint16_t* p) {
+  if constexpr (VEC == 4) {
+    const mma_u32x2 t = __builtin_nontemporal_load(reinterpret_cast<const mma_u32x2*>(p));
+    return widen_bf16x4(t[0], t[1]);
+  } else {
+    Vec<1> r; r.v[0] = __uint_as_float((uint32_t)__builtin_nontemporal_load(p) << 16); return r;
+  }
+}
+
 // 1 byte per element (selection codes, explicit keep masks)
 template <int VEC> __device__ __forceinline__ uint32_t ldb(const uint8_t* p);
 template <> __device__ __forceinline__ uint32_t ldb<4>(const uint8_t* p) { return *reinterpret_cast<const uint32_t*>(p); }

@@ -24,34 +24,8 @@
 namespace mma {
 
 // The logit tables P and Q are held as TT = float, or as bf16 in uint16_t (the `_h` entry points): a compile-time parameter of the
-// param structs and of the K1 / K2b kernels.  A bf16 row is read 4 columns per lane as ONE 8-byte load (VEC = 4) or as scalar 2-byte
-// loads (VEC = 1) and widened with bits << 16, which is exact: everything behind the load is the fp32 code, whatever TT is.
-typedef uint32_t mma_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ Vec<4> widen_bf16x4(uint32_t lo, uint32_t hi) {
-  Vec<4> r;
-  r.v[0] = __uint_as_float(lo << 16); r.v[1] = __uint_as_float(lo & 0xFFFF0000u);
-  r.v[2] = __uint_as_float(hi << 16); r.v[3] = __uint_as_float(hi & 0xFFFF0000u);
-  return r;
-}
-template <int VEC> __device__ __forceinline__ Vec<VEC> ldt(const float* p) { return ldv<VEC>(p); }
-template <int VEC> __device__ __forceinline__ Vec<VEC> ldt_nt(const float* p) { return ldv_nt<VEC>(p); }
-template <int VEC> __device__ __forceinline__ Vec<VEC> ldt(const uint16_t* p) {
-  if constexpr (VEC == 4) {
-    const uint2 t = *reinterpret_cast<const uint2*>(p);
-    return widen_bf16x4(t.x, t.y);
-  } else {
-    Vec<1> r; r.v[0] = __uint_as_float((uint32_t)*p << 16); return r;
-  }
-}
-template <int VEC> __device__ __forceinline__ Vec<VEC> ldt_nt(const uint16_t* p) {
-  if constexpr (VEC == 4) {
-    const mma_u32x2 t = __builtin_nontemporal_load(reinterpret_cast<const mma_u32x2*>(p));
-    return widen_bf16x4(t[0], t[1]);
-  } else {
-    Vec<1> r; r.v[0] = __uint_as_float((uint32_t)__builtin_nontemporal_load(p) << 16); return r;
-  }
-}
-
+// param structs and of the K1 / K2b kernels.  The row loads are ldt / ldt_nt of common.h (shared with the std kernels of
+// nc_moments.hip): everything behind the load is the fp32 code, whatever TT is.
 template <class TT>
 struct NcFwdParamsT {
   const float* x; int64_t ldx;

@@ -1,5 +1,5 @@
-// K1s / K2s: the second-moment ("std") aggregator of the node-classification layer (include/mma_amd.h, ABI 37; DESIGN.md "std
-// aggregator"), hand-written for gfx950.  One mask, a kernel pair of its own on the NCGraph plan of K1 / K2b (nc_fused.hip):
+// K1s / K2s: the second-moment ("std") aggregator of the node-classification layer (include/mma_amd.h, ABI 37, bf16 tables: ABI 40;
+// DESIGN.md "std aggregator"), hand-written for gfx950.  One mask, a kernel pair of its own on the NCGraph plan of K1 / K2b (nc_fused.hip):
 //
 //   forward   one pass over the by-target items: s1 = sum_j mu, s2 = sum_j mu^2 with mu = drop * a(P[i] + Q[j]) * x_j - and, when the
 //             backward will run, T1 = sum_j drop x_j a' and T2 = sum_j mu drop x_j a' next to them, so that dL/dP is element-wise per node;
@@ -15,6 +15,11 @@
 // multiplies the rounding of fp32 sums into dL/dP (DESIGN.md "std aggregator").
 // The accumulator set (four sums of one mask instead of one or two sums of K) and the gradient (it depends on the edge's own message,
 // not on a per-target constant) are why this is not another instantiation of K1 / K2b.
+// The logit tables P and Q are held as TT = float, or as bf16 in uint16_t (mma_nc_std_fwd_h / mma_nc_std_bwd_h): a compile-time
+// parameter of the param structs and kernels, as in nc_fused.hip.  Exactly four loads see it (ldt / ldt_nt of common.h) - the forward's
+// own P row and gathered Q rows, the backward's own Q row and gathered P rows; a value is widened with bits << 16, which is exact, so
+// everything behind the load - the fp64 sums, x, g r, mean, every gradient - is the fp32 code, and the backward recomputes z from
+// exactly what the forward read.
 #include <type_traits>
 #include "common.h"
 
@@ -22,9 +27,10 @@ namespace mma {
 
 constexpr float kStdEps = 1e-5f;      // layers.py:735
 
+template <class TT>
 struct NcStdFwdParams {
   const float* x; int64_t ldx;
-  const float* P; int64_t ldp; const float* Q; int64_t ldq;
+  const TT* P; int64_t ldp; const TT* Q; int64_t ldq;       // pitches in elements
   const int32_t* rowptr; const int32_t* col;
   const int4* items; int64_t n_items;
   double* partial; int64_t pstride;  // fp64 values per slot: [s1 | s2] (2H), saving: [s1 | s2 | T1 | T2] (4H)
@@ -74,8 +80,8 @@ template <int VEC> __device__ __forceinline__ void std_dstore(double* p, const D
 }
 
 // the combine of one (node, VEC columns) from its full-segment sums
-template <int VEC, bool SAVE>
-__device__ __forceinline__ void nc_std_write(const NcStdFwdParams& p, int node, int c, const DVec<VEC>& s1, const DVec<VEC>& s2,
+template <int VEC, bool SAVE, class TT>
+__device__ __forceinline__ void nc_std_write(const NcStdFwdParams<TT>& p, int node, int c, const DVec<VEC>& s1, const DVec<VEC>& s2,
                                              const DVec<VEC>& t1, const DVec<VEC>& t2) {
   const double d = (double)max(p.rowptr[node + 1] - p.rowptr[node], 1);
   Vec<VEC> mo, mean, r, coef;
@@ -103,8 +109,8 @@ __device__ __forceinline__ void nc_std_write(const NcStdFwdParams& p, int node, 
 }
 
 // MULTI = false: one item per wavefront; MULTI = true: one item per group of G = LPR lanes (see nc_fwd_body in nc_fused.hip)
-template <int VEC, bool SAVE, int DM, bool MULTI>
-__global__ __launch_bounds__(kBlock, 2) void nc_std_fwd_kernel(const NcStdFwdParams p) {
+template <int VEC, bool SAVE, int DM, bool MULTI, class TT>
+__global__ __launch_bounds__(kBlock, 2) void nc_std_fwd_kernel(const NcStdFwdParams<TT> p) {
   const DropParams dp = (DM == MMA_DROP_HASH || DM == MMA_DROP_HASH16) ? drop_resolve(p.drop) : p.drop;
   constexpr int U = 2;                          // edge steps in flight per lane
   const int lane = threadIdx.x & (kWave - 1);
@@ -146,7 +152,7 @@ __global__ __launch_bounds__(kBlock, 2) void nc_std_fwd_kernel(const NcStdFwdPar
       maxlen = __builtin_amdgcn_readfirstlane(maxlen);
     }
 
-    const Vec<VEC> pi = ldv_nt<VEC>(p.P + std_row_off(node, p.ldp) + cc);
+    const Vec<VEC> pi = ldt_nt<VEC>(p.P + std_row_off(node, p.ldp) + cc);
     DVec<VEC> s1 = dzero<VEC>(), s2 = dzero<VEC>(), t1 = dzero<VEC>(), t2 = dzero<VEC>();
 
     for (int base = 0; base < maxlen; base += G) {
@@ -162,7 +168,7 @@ __global__ __launch_bounds__(kBlock, 2) void nc_std_fwd_kernel(const NcStdFwdPar
           const int j = __shfl(myj, gbase + (tt[u] & (G - 1)), kWave);
           const int jj = ev[u] ? j : node;     // inactive sub-rows re-read the item's own rows (cached); zeroed by the select below
           xj[u] = ldv<VEC>(p.x + std_row_off(jj, p.ldx) + cc);
-          qv[u] = ldv<VEC>(p.Q + std_row_off(jj, p.ldq) + cc);
+          qv[u] = ldt<VEC>(p.Q + std_row_off(jj, p.ldq) + cc);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -223,8 +229,8 @@ __global__ __launch_bounds__(kBlock, 2) void nc_std_fwd_kernel(const NcStdFwdPar
 }
 
 // hub nodes: the chunk partials summed in slot order (fixed: bitwise repeatable), then the same combine
-template <int VEC, bool SAVE>
-__global__ __launch_bounds__(kBlock) void nc_std_fwd_finalize_kernel(const NcStdFwdParams p, const int4* hubs, int64_t n_hubs) {
+template <int VEC, bool SAVE, class TT>
+__global__ __launch_bounds__(kBlock) void nc_std_fwd_finalize_kernel(const NcStdFwdParams<TT> p, const int4* hubs, int64_t n_hubs) {
   const int per_row = (p.H + VEC - 1) / VEC;
   const int64_t total = n_hubs * per_row;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
@@ -274,9 +280,10 @@ __global__ __launch_bounds__(kBlock) void nc_std_bwd_node_kernel(const NcStdNode
 
 // ------------------------------------------------------------------------------------------------------
 // backward, edge level, over the transposed CSR (grouped by source j)
+template <class TT>
 struct NcStdBwdParams {
   const float* x; int64_t ldx;
-  const float* P; int64_t ldp; const float* Q; int64_t ldq;
+  const TT* P; int64_t ldp; const TT* Q; int64_t ldq;
   const float* gr; int64_t ldgr; const float* mean; int64_t ldsv;      // mean = the first H columns of the saved rows
   const int32_t* t_col; const int32_t* t_eid;
   const int4* items; int64_t n_items;
@@ -286,8 +293,8 @@ struct NcStdBwdParams {
   DropParams drop;
 };
 
-template <int VEC, int DM, bool MULTI>
-__global__ __launch_bounds__(kBlock, 2) void nc_std_bwd_kernel(const NcStdBwdParams p) {
+template <int VEC, int DM, bool MULTI, class TT>
+__global__ __launch_bounds__(kBlock, 2) void nc_std_bwd_kernel(const NcStdBwdParams<TT> p) {
   constexpr bool DROP = DM != MMA_DROP_NONE;
   const DropParams dp = (DM == MMA_DROP_HASH || DM == MMA_DROP_HASH16) ? drop_resolve(p.drop) : p.drop;
   constexpr int U = 2;
@@ -331,7 +338,7 @@ __global__ __launch_bounds__(kBlock, 2) void nc_std_bwd_kernel(const NcStdBwdPar
     }
 
     const Vec<VEC> xj = ldv_nt<VEC>(p.x + std_row_off(node, p.ldx) + cc);
-    const Vec<VEC> qj = ldv_nt<VEC>(p.Q + std_row_off(node, p.ldq) + cc);
+    const Vec<VEC> qj = ldt_nt<VEC>(p.Q + std_row_off(node, p.ldq) + cc);
     Vec<VEC> aq = vzero<VEC>(), ax = vzero<VEC>();
 
     for (int base = 0; base < maxlen; base += G) {
@@ -352,7 +359,7 @@ __global__ __launch_bounds__(kBlock, 2) void nc_std_bwd_kernel(const NcStdBwdPar
           const int tl = min(tt, max(cnt - 1, 0));
           const int ii = __shfl(myi, gbase + (tl & (G - 1)), kWave);
           eid[u] = DROP ? (uint32_t)__shfl(mye, gbase + (tl & (G - 1)), kWave) : 0u;
-          pv[u] = ldv<VEC>(p.P + std_row_off(ii, p.ldp) + cc);
+          pv[u] = ldt<VEC>(p.P + std_row_off(ii, p.ldp) + cc);
           gv[u] = ldv<VEC>(p.gr + std_row_off(ii, p.ldgr) + cc);
           mv[u] = ldv<VEC>(p.mean + std_row_off(ii, p.ldsv) + cc);
         }
@@ -404,8 +411,8 @@ __global__ __launch_bounds__(kBlock, 2) void nc_std_bwd_kernel(const NcStdBwdPar
   }
 }
 
-template <int VEC>
-__global__ __launch_bounds__(kBlock) void nc_std_bwd_finalize_kernel(const NcStdBwdParams p, const int4* hubs, int64_t n_hubs) {
+template <int VEC, class TT>
+__global__ __launch_bounds__(kBlock) void nc_std_bwd_finalize_kernel(const NcStdBwdParams<TT> p, const int4* hubs, int64_t n_hubs) {
   const int per_row = (p.H + VEC - 1) / VEC;
   const int64_t total = n_hubs * per_row;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
@@ -433,6 +440,14 @@ __global__ __launch_bounds__(kBlock) void nc_std_bwd_finalize_kernel(const NcStd
 // copies because that file is left untouched here.  Follow-up: hoist nc_common_checks / nc_item_checks / nc_item_alignment, make_drop,
 // geometry, item_grid and elementwise_grid into common.h and have both files use them, so that the two copies cannot drift.
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// a logit table's vector condition: one lane reads 4 elements at once - 16 bytes of fp32, 8 bytes of bf16
+template <class TT> static bool table_aligned(const TT* p) { return (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(TT) - 1)) == 0; }
+// a bf16 table at an odd address cannot be read at all (the scalar form loads 2-byte elements); fp32 tables are taken as they always were
+template <class TT> static int std_table_checks(const TT* P, const TT* Q) {
+  MMA_REQUIRE(sizeof(TT) != 2 || ((reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(Q)) & 1u) == 0,
+              "bf16 tables P / Q at an odd address: they need 2-byte alignment");
+  return 0;
+}
 
 static int nc_common_checks(int64_t N, int64_t E, int32_t H) {
   MMA_REQUIRE(N >= 0 && E >= 0 && N < (1LL << 31) && E < (1LL << 31), "N=%lld E=%lld out of int32 range", (long long)N, (long long)E);
@@ -510,8 +525,10 @@ static void std_for_parts(const int32_t* items, int64_t n_items, int64_t n_wave_
 
 using namespace mma;
 
-extern "C" int mma_nc_std_fwd(
-    const float* x, int64_t ldx, const float* P, int64_t ldp, const float* Q, int64_t ldq,
+// mma_nc_std_fwd (TT = float) and mma_nc_std_fwd_h (TT = uint16_t: bf16 tables, pitches in elements)
+template <class TT>
+static int nc_std_fwd(
+    const float* x, int64_t ldx, const TT* P, int64_t ldp, const TT* Q, int64_t ldq,
     const int32_t* rowptr, const int32_t* col,
     const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
     double* partial, int64_t n_slots, float* m, int64_t ldms, float* saved, int64_t ldt,
@@ -530,14 +547,15 @@ extern "C" int mma_nc_std_fwd(
   if (N == 0 || n_items == 0) return 0;
   MMA_REQUIRE(x && P && Q && rowptr && items && m, "NULL argument");
   MMA_REQUIRE(E == 0 || col != nullptr, "NULL col");
+  if (int rc = std_table_checks(P, Q)) return rc;
   if (int rc = nc_item_alignment(items, hubs)) return rc;
   MMA_REQUIRE((reinterpret_cast<uintptr_t>(partial) & 7u) == 0, "partial must be 8-byte aligned (fp64 sums)");
-  NcStdFwdParams p{};
+  NcStdFwdParams<TT> p{};
   if (int rc = std_make_drop(drop_mode, drop_thr, seed, seed_dev, drop_edge_base, keep, E, &p.drop)) return rc;
   const int dm = std_drop_form(drop_mode, drop_thr, E, p.drop);
   const bool save = saved != nullptr;
   const bool v4 = (H % 4 == 0) && (ldx % 4 == 0) && (ldp % 4 == 0) && (ldq % 4 == 0) && (ldms % 4 == 0) && (!save || ldt % 4 == 0) &&
-                  aligned16(x) && aligned16(P) && aligned16(Q) && aligned16(m) && (!save || aligned16(saved)) &&
+                  aligned16(x) && table_aligned(P) && table_aligned(Q) && aligned16(m) && (!save || aligned16(saved)) &&
                   (partial == nullptr || aligned16(partial));
   const StdGeometry g = std_geometry(H, v4);
   p.x = x; p.ldx = ldx; p.P = P; p.ldp = ldp; p.Q = Q; p.ldq = ldq; p.rowptr = rowptr; p.col = col;
@@ -548,7 +566,7 @@ extern "C" int mma_nc_std_fwd(
   std_for_parts(items, n_items, n_wave_items, g, [&](const int4* it, int64_t cnt, bool multi, dim3 grid) {
     p.items = it; p.n_items = cnt;
     with_flag(g.vec == 4, [&](auto v) { with_flag(save, [&](auto sv) { with_dm(dm, [&](auto d) { with_flag(multi, [&](auto mu) {
-      hipLaunchKernelGGL((nc_std_fwd_kernel<decltype(v)::value ? 4 : 1, decltype(sv)::value, decltype(d)::value, decltype(mu)::value>),
+      hipLaunchKernelGGL((nc_std_fwd_kernel<decltype(v)::value ? 4 : 1, decltype(sv)::value, decltype(d)::value, decltype(mu)::value, TT>),
                          grid, dim3(kBlock), 0, st, p);
     }); }); }); });
   });
@@ -557,7 +575,7 @@ extern "C" int mma_nc_std_fwd(
     const int per_row = (H + g.vec - 1) / g.vec;
     const int4* hb = reinterpret_cast<const int4*>(hubs);
     with_flag(g.vec == 4, [&](auto v) { with_flag(save, [&](auto sv) {
-      hipLaunchKernelGGL((nc_std_fwd_finalize_kernel<decltype(v)::value ? 4 : 1, decltype(sv)::value>), elementwise_grid(n_hubs * per_row),
+      hipLaunchKernelGGL((nc_std_fwd_finalize_kernel<decltype(v)::value ? 4 : 1, decltype(sv)::value, TT>), elementwise_grid(n_hubs * per_row),
                          dim3(kBlock), 0, st, p, hb, n_hubs);
     }); });
     if (int rc = check_launch("nc_std_fwd_finalize_kernel")) return rc;
@@ -565,8 +583,10 @@ extern "C" int mma_nc_std_fwd(
   return 0;
 }
 
-extern "C" int mma_nc_std_bwd(
-    const float* x, int64_t ldx, const float* P, int64_t ldp, const float* Q, int64_t ldq,
+// mma_nc_std_bwd (TT = float) and mma_nc_std_bwd_h (TT = uint16_t)
+template <class TT>
+static int nc_std_bwd(
+    const float* x, int64_t ldx, const TT* P, int64_t ldp, const TT* Q, int64_t ldq,
     const float* g, int64_t ldg, const float* saved, int64_t ldt, float* gr, int64_t ldgr, float* gP, int64_t ldgp, int64_t n_targets,
     const int32_t* t_col, const int32_t* t_eid,
     const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
@@ -587,12 +607,13 @@ extern "C" int mma_nc_std_bwd(
   MMA_REQUIRE(n_targets >= 1 && n_targets <= N, "n_targets=%lld: 1 <= n_targets <= N=%lld", (long long)n_targets, (long long)N);
   MMA_REQUIRE(x && P && Q && g && saved && gr && gP && items && gQ && gx, "NULL argument");
   MMA_REQUIRE(E == 0 || (t_col != nullptr && t_eid != nullptr), "NULL transposed CSR");
+  if (int rc = std_table_checks(P, Q)) return rc;
   if (int rc = nc_item_alignment(items, hubs)) return rc;
-  NcStdBwdParams p{};
+  NcStdBwdParams<TT> p{};
   if (int rc = std_make_drop(drop_mode, drop_thr, seed, seed_dev, drop_edge_base, keep, E, &p.drop)) return rc;
   const int dm = std_drop_form(drop_mode, drop_thr, E, p.drop);
   const bool v4 = (H % 4 == 0) && (ldx % 4 == 0) && (ldp % 4 == 0) && (ldq % 4 == 0) && (ldg % 4 == 0) && (ldt % 4 == 0) && (ldgr % 4 == 0) &&
-                  (ldgp % 4 == 0) && (ldgq % 4 == 0) && (ldgx % 4 == 0) && aligned16(x) && aligned16(P) && aligned16(Q) && aligned16(g) &&
+                  (ldgp % 4 == 0) && (ldgq % 4 == 0) && (ldgx % 4 == 0) && aligned16(x) && table_aligned(P) && table_aligned(Q) && aligned16(g) &&
                   aligned16(saved) && aligned16(gr) && aligned16(gP) && aligned16(gQ) && aligned16(gx) && (partial == nullptr || aligned16(partial));
   const StdGeometry geo = std_geometry(H, v4);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -611,16 +632,67 @@ extern "C" int mma_nc_std_bwd(
   std_for_parts(items, n_items, n_wave_items, geo, [&](const int4* it, int64_t cnt, bool multi, dim3 grid) {
     p.items = it; p.n_items = cnt;
     with_flag(geo.vec == 4, [&](auto v) { with_dm(dm, [&](auto d) { with_flag(multi, [&](auto mu) {
-      hipLaunchKernelGGL((nc_std_bwd_kernel<decltype(v)::value ? 4 : 1, decltype(d)::value, decltype(mu)::value>), grid, dim3(kBlock), 0, st, p);
+      hipLaunchKernelGGL((nc_std_bwd_kernel<decltype(v)::value ? 4 : 1, decltype(d)::value, decltype(mu)::value, TT>), grid, dim3(kBlock), 0, st, p);
     }); }); });
   });
   if (int rc = check_launch("nc_std_bwd_kernel")) return rc;
   if (n_hubs > 0) {
     const int4* hb = reinterpret_cast<const int4*>(hubs);
     const dim3 fg = elementwise_grid(n_hubs * per_row);
-    if (geo.vec == 4) hipLaunchKernelGGL((nc_std_bwd_finalize_kernel<4>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
-    else hipLaunchKernelGGL((nc_std_bwd_finalize_kernel<1>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
+    if (geo.vec == 4) hipLaunchKernelGGL((nc_std_bwd_finalize_kernel<4, TT>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
+    else hipLaunchKernelGGL((nc_std_bwd_finalize_kernel<1, TT>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
     if (int rc = check_launch("nc_std_bwd_finalize_kernel")) return rc;
   }
   return 0;
 }
+
+#define NC_STD_FWD_ARGS x, ldx, P, ldp, Q, ldq, rowptr, col, items, n_items, n_wave_items, hubs, n_hubs, partial, n_slots, m, ldms, saved, ldt, \
+                        N, E, H, act_host, drop_mode, drop_thr, seed, seed_dev, drop_edge_base, keep, stream
+extern "C" int mma_nc_std_fwd(
+    const float* x, int64_t ldx, const float* P, int64_t ldp, const float* Q, int64_t ldq,
+    const int32_t* rowptr, const int32_t* col,
+    const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
+    double* partial, int64_t n_slots, float* m, int64_t ldms, float* saved, int64_t ldt,
+    int64_t N, int64_t E, int32_t H, const uint8_t* act_host,
+    int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
+    void* stream) {
+  return nc_std_fwd<float>(NC_STD_FWD_ARGS);
+}
+extern "C" int mma_nc_std_fwd_h(
+    const float* x, int64_t ldx, const uint16_t* P, int64_t ldp, const uint16_t* Q, int64_t ldq,
+    const int32_t* rowptr, const int32_t* col,
+    const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
+    double* partial, int64_t n_slots, float* m, int64_t ldms, float* saved, int64_t ldt,
+    int64_t N, int64_t E, int32_t H, const uint8_t* act_host,
+    int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
+    void* stream) {
+  return nc_std_fwd<uint16_t>(NC_STD_FWD_ARGS);
+}
+#undef NC_STD_FWD_ARGS
+
+#define NC_STD_BWD_ARGS x, ldx, P, ldp, Q, ldq, g, ldg, saved, ldt, gr, ldgr, gP, ldgp, n_targets, t_col, t_eid, items, n_items, n_wave_items, \
+                        hubs, n_hubs, partial, n_slots, gQ, ldgq, gx, ldgx, N, E, H, act_host, drop_mode, drop_thr, seed, seed_dev, \
+                        drop_edge_base, keep, stream
+extern "C" int mma_nc_std_bwd(
+    const float* x, int64_t ldx, const float* P, int64_t ldp, const float* Q, int64_t ldq,
+    const float* g, int64_t ldg, const float* saved, int64_t ldt, float* gr, int64_t ldgr, float* gP, int64_t ldgp, int64_t n_targets,
+    const int32_t* t_col, const int32_t* t_eid,
+    const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
+    float* partial, int64_t n_slots, float* gQ, int64_t ldgq, float* gx, int64_t ldgx,
+    int64_t N, int64_t E, int32_t H, const uint8_t* act_host,
+    int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
+    void* stream) {
+  return nc_std_bwd<float>(NC_STD_BWD_ARGS);
+}
+extern "C" int mma_nc_std_bwd_h(
+    const float* x, int64_t ldx, const uint16_t* P, int64_t ldp, const uint16_t* Q, int64_t ldq,
+    const float* g, int64_t ldg, const float* saved, int64_t ldt, float* gr, int64_t ldgr, float* gP, int64_t ldgp, int64_t n_targets,
+    const int32_t* t_col, const int32_t* t_eid,
+    const int32_t* items, int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs,
+    float* partial, int64_t n_slots, float* gQ, int64_t ldgq, float* gx, int64_t ldgx,
+    int64_t N, int64_t E, int32_t H, const uint8_t* act_host,
+    int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, int64_t drop_edge_base, const uint8_t* keep,
+    void* stream) {
+  return nc_std_bwd<uint16_t>(NC_STD_BWD_ARGS);
+}
+#undef NC_STD_BWD_ARGS

@@ -370,76 +370,151 @@ def nc_fused_aggregate(x, P, Q, graph, kinds, acts, drop=None, reduce_k=False, l
     return _NCFused.apply(x, P, Q, graph, tuple(kinds), tuple(acts), drop or DropoutSpec(0.0), bool(reduce_k), logit_dtype)
 
 
+def nc_std_fwd_launch(x_src, P, Q, graph, act, drop, save):
+    """K1s on prepared operands -> (m, saved).  No autograd; shared by _NCStd and _NCStdLocal.  P and Q are both fp32, or both bf16 (the
+    `_h` entry point, ABI 40: half the bytes of the per-edge logit gather); either may be a column block of a wider buffer."""
+    entry = _nc_entry("mma_nc_std_fwd", P, Q)
+    S, H = x_src.shape
+    N, E = graph.N, graph.E
+    assert x_src.dtype == torch.float32
+    assert S == graph.n_src and P.shape == (N, H) and Q.shape == (S, H)
+    assert x_src.is_contiguous() and P.stride(1) == 1 and Q.stride(1) == 1
+    dev = x_src.device
+    tb = P.element_size()                                                                       # bytes per table element
+    m = torch.empty((N, H), device=dev, dtype=torch.float32)
+    saved = torch.empty((N, 3 * H), device=dev, dtype=torch.float32) if save else None        # [mean | r | r (T2 - mean T1)]
+    # hub chunk partials: the two (saving: four) sums per column, held in fp64
+    partial = torch.empty((graph.n_slots, (4 if save else 2) * H), device=dev, dtype=torch.float64) if graph.n_slots else None
+    if drop.keep is not None:
+        assert drop.keep.dtype == torch.uint8 and drop.keep.is_contiguous() and drop.keep.is_cuda and \
+            tuple(drop.keep.shape) == (1, E, H), "explicit keep mask must be a contiguous (1,E,H) uint8 GPU tensor"
+    mode, thr, seed, seed_dev, keep = drop.args()
+    # per edge: the source id and the gathered x_j and Q_j rows; per target: its item, the P row, m and the saved rows
+    with _span("nc_std_fwd", nbytes=E * (4 + (4 + tb) * H) + N * (16 + (4 + tb) * H + (12 * H if save else 0)), flops=(14 if save else 9) * E * H):
+        call(entry, ptr(x_src), x_src.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0),
+             ptr(graph.rowptr), ptr(graph.col), ptr(graph.items), graph.items.shape[0], graph.n_wave_items,
+             ptr(graph.hubs) if graph.n_slots else None, graph.hubs.shape[0] if graph.n_slots else 0, ptr(partial), graph.n_slots,
+             ptr(m), H, ptr(saved), 3 * H if save else 0, N, E, H, host_codes([act]),
+             mode, thr, seed, seed_dev, graph.edge_base, keep, stream_ptr())
+    return m, saved
+
+
+def nc_std_bwd_launch(x_src, P, Q, g, saved, graph, act, drop, gP, gQ, gx):
+    """K2s (node pass + edge pass over the transposed lists) into gP (N,H), gQ (n_src,H), gx (n_src,H); gP / gQ may be column blocks of
+    a wider buffer.  P and Q: the tables the forward read, fp32 or bf16 (z is recomputed from the same stored values)."""
+    entry = _nc_entry("mma_nc_std_bwd", P, Q)
+    S, H = x_src.shape
+    N, E = graph.N, graph.E
+    dev = g.device
+    tb = P.element_size()
+    gr = torch.empty((N, H), device=dev, dtype=torch.float32)
+    n_slots = graph.t_n_slots
+    partial = torch.empty((n_slots, 2 * H), device=dev, dtype=torch.float32) if n_slots else None
+    mode, thr, seed, seed_dev, keep = drop.args()
+    # per edge: target id, edge id and the gathered P, g r and mean rows; per source: its item, x_j and Q_j in, gQ and gx out;
+    # per target (node pass): g and the saved r / coefficient rows in, g r and gP out
+    with _span("nc_std_bwd", nbytes=E * (8 + (8 + tb) * H) + S * (16 + (12 + tb) * H) + N * 20 * H, flops=13 * E * H):
+        call(entry, ptr(x_src), x_src.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0),
+             ptr(g), g.stride(0), ptr(saved), saved.stride(0), ptr(gr), H, ptr(gP), gP.stride(0), N,
+             ptr(graph.t_col), ptr(graph.t_eid), ptr(graph.t_items), graph.t_items.shape[0], graph.t_n_wave_items,
+             ptr(graph.t_hubs) if n_slots else None, graph.t_hubs.shape[0] if n_slots else 0, ptr(partial), n_slots,
+             ptr(gQ), gQ.stride(0), ptr(gx), H, S, E, H, host_codes([act]), mode, thr, seed, seed_dev, graph.edge_base, keep, stream_ptr())
+
+
 class _NCStd(torch.autograd.Function):
     """m = sqrt(relu(E_j[mu^2] - E_j[mu]^2) + 1e-5), mu = drop(act(P[i] + Q[j])) * x_j over the neighbours j of target i: the
     second-moment aggregator (K1s forward, K2s backward; include/mma_amd.h ABI 37, DESIGN.md "std aggregator").  Shaped like
-    _NCFused: inputs x_src, P, Q, backward returns gx, gP, gQ."""
+    _NCFused: inputs x_src, P, Q, backward returns gx, gP, gQ; logit_dtype as there - torch.bfloat16 converts fp32 tables once
+    (mma_rows_to_bf16), the kernels gather and the backward keeps the bf16 tables (ABI 40), gP / gQ come back in fp32 as the gradients
+    with respect to the stored values (straight-through)."""
 
     @staticmethod
-    def forward(ctx, x_src, P, Q, graph, act, drop):
+    def forward(ctx, x_src, P, Q, graph, act, drop, logit_dtype=None):
+        _nc_entry("mma_nc_std_fwd", P, Q)                   # the storage checks need no GPU: they come first
+        convert = logit_dtype is not None and check_logit_dtype(logit_dtype) != P.dtype
+        if convert and logit_dtype != torch.bfloat16:
+            raise ValueError("bf16 logit tables cannot be widened back: pass logit_dtype=None or torch.bfloat16 with them")
         require_gpu(x_src, P, Q)
         x_src = x_src.contiguous()
         if P.stride(1) != 1:
             P = P.contiguous()
         if Q.stride(1) != 1:
             Q = Q.contiguous()
-        S, H = x_src.shape
-        N, E = graph.N, graph.E
-        assert x_src.dtype == torch.float32 and P.dtype == torch.float32 and Q.dtype == torch.float32
-        assert S == graph.n_src and P.shape == (N, H) and Q.shape == (S, H)
-        dev = x_src.device
-        save = any(ctx.needs_input_grad[:3])
-        m = torch.empty((N, H), device=dev, dtype=torch.float32)
-        saved = torch.empty((N, 3 * H), device=dev, dtype=torch.float32) if save else None        # [mean | r | r (T2 - mean T1)]
-        # hub chunk partials: the two (saving: four) sums per column, held in fp64
-        partial = torch.empty((graph.n_slots, (4 if save else 2) * H), device=dev, dtype=torch.float64) if graph.n_slots else None
-        if drop.keep is not None:
-            assert drop.keep.dtype == torch.uint8 and drop.keep.is_contiguous() and drop.keep.is_cuda and \
-                tuple(drop.keep.shape) == (1, E, H), "explicit keep mask must be a contiguous (1,E,H) uint8 GPU tensor"
-        mode, thr, seed, seed_dev, keep = drop.args()
-        # per edge: the source id and the gathered x_j and Q_j rows; per target: its item, the P row, m and the saved rows
-        with _span("nc_std_fwd", nbytes=E * (4 + 8 * H) + N * (16 + 8 * H + (12 * H if save else 0)), flops=(14 if save else 9) * E * H):
-            call("mma_nc_std_fwd", ptr(x_src), x_src.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0),
-                 ptr(graph.rowptr), ptr(graph.col), ptr(graph.items), graph.items.shape[0], graph.n_wave_items,
-                 ptr(graph.hubs) if graph.n_slots else None, graph.hubs.shape[0] if graph.n_slots else 0, ptr(partial), graph.n_slots,
-                 ptr(m), H, ptr(saved), 3 * H if save else 0, N, E, H, host_codes([act]),
-                 mode, thr, seed, seed_dev, graph.edge_base, keep, stream_ptr())
+        if convert:
+            P, Q = rows_to_bf16(P), rows_to_bf16(Q)
+        m, saved = nc_std_fwd_launch(x_src, P, Q, graph, act, drop, any(ctx.needs_input_grad[:3]))
         ctx.graph, ctx.act, ctx.drop = graph, act, drop
         ctx.save_for_backward(x_src, P, Q, saved)
         return m
 
     @staticmethod
     def backward(ctx, g):
-        graph, act, drop = ctx.graph, ctx.act, ctx.drop
+        graph = ctx.graph
         x_src, P, Q, saved = ctx.saved_tensors
         S, H = x_src.shape
-        N, E = graph.N, graph.E
         dev = g.device
-        g = g.contiguous()
-        gr = torch.empty((N, H), device=dev, dtype=torch.float32)
-        gP = torch.empty((N, H), device=dev, dtype=torch.float32)
+        gP = torch.empty((graph.N, H), device=dev, dtype=torch.float32)
         gQ = torch.empty((S, H), device=dev, dtype=torch.float32)
         gx = torch.empty((S, H), device=dev, dtype=torch.float32)
-        n_slots = graph.t_n_slots
-        partial = torch.empty((n_slots, 2 * H), device=dev, dtype=torch.float32) if n_slots else None
-        mode, thr, seed, seed_dev, keep = drop.args()
-        # per edge: target id, edge id and the gathered P, g r and mean rows; per source: its item, x_j and Q_j in, gQ and gx out;
-        # per target (node pass): g and the saved r / coefficient rows in, g r and gP out
-        with _span("nc_std_bwd", nbytes=E * (8 + 12 * H) + S * (16 + 16 * H) + N * 20 * H, flops=13 * E * H):
-            call("mma_nc_std_bwd", ptr(x_src), x_src.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0),
-                 ptr(g), g.stride(0), ptr(saved), saved.stride(0), ptr(gr), H, ptr(gP), H, N,
-                 ptr(graph.t_col), ptr(graph.t_eid), ptr(graph.t_items), graph.t_items.shape[0], graph.t_n_wave_items,
-                 ptr(graph.t_hubs) if n_slots else None, graph.t_hubs.shape[0] if n_slots else 0, ptr(partial), n_slots,
-                 ptr(gQ), H, ptr(gx), H, S, E, H, host_codes([act]), mode, thr, seed, seed_dev, graph.edge_base, keep, stream_ptr())
-        return gx, gP, gQ, None, None, None
+        nc_std_bwd_launch(x_src, P, Q, g.contiguous(), saved, graph, ctx.act, ctx.drop, gP, gQ, gx)
+        return gx, gP, gQ, None, None, None, None
 
 
-def nc_std_aggregate(x, P, Q, graph, act=ACT_SIGMOID, drop=None):
+def nc_std_aggregate(x, P, Q, graph, act=ACT_SIGMOID, drop=None, logit_dtype=None):
     """The second-moment aggregator of one mask -> m (graph.N, H): the standard deviation, per feature column, of the masked neighbour
     messages drop(act(P[i] + Q[j])) * x_j of every target i (no self term; an isolated node gives sqrt(1e-5)).
     x: (graph.n_src, H); P = x[:N] @ W[:H] (N, H), Q = x @ W[H:] (n_src, H); act: ACT_SIGMOID, or ACT_RAW for the raw logits;
-    drop: a DropoutSpec whose explicit keep mask, if any, is (1, E, H)."""
-    return _NCStd.apply(x, P, Q, graph, int(act), drop or DropoutSpec(0.0))
+    drop: a DropoutSpec whose explicit keep mask, if any, is (1, E, H).  logit_dtype: None keeps the tables as given (fp32, or bf16
+    both); torch.bfloat16 rounds fp32 tables once and gathers the bf16 copies (see _NCStd)."""
+    return _NCStd.apply(x, P, Q, graph, int(act), drop or DropoutSpec(0.0), logit_dtype)
+
+
+class _NCStdLocal(torch.autograd.Function):
+    """m_std from (x, W) in one autograd node, the std counterpart of _NCLocalLayer: owns its GEMMs, so P and Q (and their gradients)
+    are the column halves of ONE (N,2H) buffer - one forward GEMM that leaves [P | Q] in `logit_dtype`, one dL/dx GEMM over the
+    concatenated [gP | gQ], one dW GEMM.  The [P | Q] buffer (bf16: half the size) is what is saved."""
+
+    @staticmethod
+    def forward(ctx, x, w, graph, act, drop, logit_dtype=torch.float32):
+        from .dense import mm_into
+        require_gpu(x, w)
+        x = x.contiguous()
+        N, H = x.shape
+        assert w.shape == (2 * H, H)
+        PQ = torch.empty((N, 2 * H), device=x.device, dtype=check_logit_dtype(logit_dtype))
+        wcat = torch.cat([w[:H], w[H:]], 1)                                 # (H, 2H) = [W[:H] | W[H:]]
+        need = any(ctx.needs_input_grad[:2])
+        box = [] if need else None                                          # row maxima of x, when the forward GEMM forms them
+        mm_into(x, wcat, PQ, row_max_box=box)                               # bf16: rounded in the GEMM's epilogue where it has one
+        m, saved = nc_std_fwd_launch(x, PQ[:, :H], PQ[:, H:], graph, act, drop, need)
+        ctx.graph, ctx.act, ctx.drop = graph, act, drop
+        ctx.save_for_backward(x, PQ, saved, wcat, box[0] if box else None)
+        return m
+
+    @staticmethod
+    def backward(ctx, g):
+        from .dense import rows_mm_add_, xt_g
+        x, PQ, saved, wcat, x_row_max = ctx.saved_tensors
+        N, H = x.shape
+        gPQ = torch.empty((N, 2 * H), device=g.device, dtype=torch.float32)
+        gx = torch.empty((N, H), device=g.device, dtype=torch.float32)
+        nc_std_bwd_launch(x, PQ[:, :H], PQ[:, H:], g.contiguous(), saved, ctx.graph, ctx.act, ctx.drop, gPQ[:, :H], gPQ[:, H:], gx)
+        rows_mm_add_(gx, gPQ, wcat.t())                                     # direct + through P and Q in one GEMM (C += A B)
+        gw = None
+        if ctx.needs_input_grad[1]:
+            gcat = xt_g(x, gPQ, x_row_max)                                  # (H, 2H) = [gW[:H] | gW[H:]]
+            gw = torch.cat([gcat[:, :H], gcat[:, H:]], 0)
+        return gx, gw, None, None, None, None
+
+
+def nc_std_local(x, w, graph, act=ACT_SIGMOID, drop=None, logit_dtype=torch.float32):
+    """m_std (graph.N, H) straight from the features and the (2H, H) mask weight (unsharded graphs): nc_std_aggregate with its GEMMs
+    inside the node, as nc_local_layer is to nc_fused_aggregate.  logit_dtype=torch.bfloat16: the forward GEMM writes [P | Q] rounded
+    to bf16 (from its own epilogue on the column-group forms, else through mma_rows_to_bf16: dense.mm_into); the std kernels gather,
+    and the backward keeps, the bf16 buffer.  x, the fp64 sums and every gradient keep their types."""
+    check_logit_dtype(logit_dtype)
+    assert graph.n_src == graph.N
+    return _NCStdLocal.apply(x, w, graph, int(act), drop or DropoutSpec(0.0), logit_dtype)
 
 
 def _spmm_call(rowptr, col, val, items, hubs, n_slots, B, rows_per_block, K, bias, out, n_rows, C, n_wave_items=None):

@@ -120,8 +120,10 @@ class MMA(Module):
         logit_dtype (either strict_reference mode: a storage choice, not a semantic extension): torch.float32 (default, the path as
         it always was) or torch.bfloat16 - the mask logit tables P = x W[:H], Q = x W[H:] of the fused aggregators are rounded to
         bf16 once per call and the kernels gather, and the backward keeps, the half-size tables.  Only z = P[i] + Q[j] sees the
-        rounding; x, every sum and every gradient stay fp32.  Applies to forward() and every fused learnable_<name>(), under hash and
-        explicit dropout and under graph_capturable; the `std` aggregator and ShardedMMA keep fp32 tables."""
+        rounding; x, every sum and every gradient stay fp32.  Applies to forward() and every learnable_<name>(), under hash and
+        explicit dropout and under graph_capturable - the `std` aggregator (strict_reference=False) included: with torch.bfloat16 its
+        tables come from one GEMM of its own that writes [P | Q] in bf16 (Fn.nc_std_local), with torch.float32 it runs as it always
+        did.  ShardedMMA keeps fp32 tables."""
         super().__init__()
         self.logit_dtype = Fn.check_logit_dtype(logit_dtype)
         self.activation = activation
@@ -249,7 +251,8 @@ class MMA(Module):
                                      drop or self._drop(names, input.device), logit_dtype=self.logit_dtype)
 
     def _std(self, input, drop=None):
-        """m_std (N, H) by the second-moment kernels.  drop: this mask's own DropoutSpec (explicit keep: (1,E,H))."""
+        """m_std (N, H) by the second-moment kernels.  drop: this mask's own DropoutSpec (explicit keep: (1,E,H)).  The tables P, Q
+        are stored in self.logit_dtype."""
         if self.strict_reference:
             self._codes(["std"])                # the reference's learnable_std cannot run: NotImplementedError
         require_gpu(input)
@@ -259,6 +262,9 @@ class MMA(Module):
         if drop is None:       # learnable_std() on its own: std's slot in the layer's seed layout (see _drop)
             layout = self.aggregator_names if "std" in self.aggregator_names else ["std"]
             drop = self._std_drop(self._drop(["std"], input.device), 0, self._std_seed_slot(layout))
+        if self.logit_dtype == torch.bfloat16:
+            # one node that owns its GEMMs: the forward product leaves [P | Q] in bf16, the std kernels gather and the backward keeps it
+            return Fn.nc_std_local(input, w, self.graph(input.device), act, drop, logit_dtype=self.logit_dtype)
         return Fn.nc_std_aggregate(input, mm(input, w[:H]), mm(input, w[H:]), self.graph(input.device), act, drop)
 
     @staticmethod
