@@ -9,8 +9,7 @@
 // 64 at a time (one coalesced load) and handed to the sub-rows with ds_bpermute.  Two edge steps are
 // kept in flight per lane.  Sub-row partial sums meet in a butterfly at the end of the segment; there
 // are no atomics anywhere, so results are bitwise reproducible.
-#include <type_traits>
-#include "common.h"
+#include "nc_shared.h"
 
 #ifndef NC_FWD_UNROLL
 #define NC_FWD_UNROLL(K) ((K) >= 3 ? 1 : 2)   // measured (C4, K=4): 2 -> 1 takes 183 -> ~160 VGPRs, 2 -> 3 waves/SIMD, 5.4 -> 4.8 ms
@@ -46,10 +45,6 @@ struct NcFwdParamsT {
   const int4* hubs; int64_t n_hubs; unsigned* sync; unsigned n_slots;
 };
 using NcFwdParams = NcFwdParamsT<float>;
-
-// row * pitch as ONE v_mad_u64_u32: rows and pitches are < 2^31 (checked on the host), so the 64-bit product needs neither the
-// sign extension nor the two extra quarter-rate v_mul_lo_u32 the int * int64 form compiles to (3 multiplies per gathered row)
-__device__ __forceinline__ size_t row_off(int row, int64_t ld) { return (size_t)((uint64_t)(uint32_t)row * (uint64_t)(uint32_t)ld); }
 
 __device__ __forceinline__ int kind_of(uint32_t kinds, int k) { return (kinds >> (4 * k)) & 0xF; }
 __device__ __forceinline__ uint32_t sel_slot_of(uint32_t slots, int k) { return (slots >> (4 * k)) & 0xFu; }
@@ -851,11 +846,7 @@ __global__ __launch_bounds__(kBlock, (K <= 4 ? MMA_MIN_WAVES : 1)) void nc_bwd_s
 }
 
 // ------------------------------------------------------------------------------------------------------
-// host side
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-// a logit table's vector condition: one lane reads 4 elements at once - 16 bytes of fp32, 8 bytes of bf16
-template <class TT> static bool table_aligned(const TT* p) { return (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(TT) - 1)) == 0; }
-
+// host side: what is specific to K1 / K2a / K2b; the checks, make_drop, geometry, the grids and with_flag / with_dm are in nc_shared.h
 static int pack_codes(const uint8_t* kind_host, const uint8_t* act_host, int K, uint32_t* kinds, uint32_t* acts) {
   *kinds = 0; *acts = 0;
   for (int k = 0; k < K; ++k) {
@@ -881,43 +872,9 @@ static int64_t fill_sel_slots(const uint8_t* kind_host, int K, int H, uint32_t* 
   return ((4 + (int64_t)n * (((int64_t)H + 3) / 4)) + 3) & ~(int64_t)3;      // 64-bit: H comes straight from the caller
 }
 
-static int make_drop(int32_t mode, uint32_t thr, uint64_t seed, const uint64_t* seed_dev, int64_t edge_base, const uint8_t* keep,
-                     int64_t E, DropParams* d) {
-  d->seed_dev = seed_dev;
-  MMA_REQUIRE(edge_base >= 0 && edge_base + E < (1LL << 32), "drop_edge_base %lld out of range", (long long)edge_base);
-  d->edge_base = (uint32_t)edge_base;
-  MMA_REQUIRE(mode >= MMA_DROP_NONE && mode <= MMA_DROP_EXPLICIT, "drop_mode %d unknown", mode);
-  MMA_REQUIRE(mode == MMA_DROP_NONE || thr < 65536, "drop_thr %u out of range (0..65535: P(drop) = thr / 65536)", thr);
-  MMA_REQUIRE(mode != MMA_DROP_EXPLICIT || keep != nullptr, "drop_mode EXPLICIT needs a keep mask");
-  drop_set_threshold(d, mode, thr);
-  d->seed_lo = (uint32_t)seed; d->seed_hi = (uint32_t)(seed >> 32); d->keep = keep; d->E = E;
-  return 0;
-}
-
-struct Geometry { int vec, lpr_log, chunks; };
-// lanes per row: next power of two >= ceil(H/vec), at most one wave; wider rows take gridDim.y chunks
-static Geometry geometry(int H, bool vec4_ok) {
-  Geometry g;
-  g.vec = vec4_ok ? 4 : 1;
-  const int per_row = (H + g.vec - 1) / g.vec;
-  g.lpr_log = min(ilog2_ceil(per_row), 6);
-  g.chunks = (per_row + (1 << g.lpr_log) - 1) >> g.lpr_log;
-  return g;
-}
-
-static dim3 item_grid(int64_t n_items, int chunks, int items_per_wave = 1) {
-  const int64_t per_block = (int64_t)(kBlock / kWave) * items_per_wave;
-  int64_t blocks = (n_items + per_block - 1) / per_block;
-  if (blocks > kMaxGrid) blocks = kMaxGrid;
-  if (blocks < 1) blocks = 1;
-  return dim3((unsigned)blocks, (unsigned)chunks, 1);
-}
-
-// run-time value -> template argument: f receives it as a std::integral_constant (a generic lambda reads decltype(v)::value).
-// Only what the kernels are instantiated for is reachable: K-slices {1,2,3,4,8}; the one-launch kernels do not exist for
-// explicit masks (EXPLICIT_OK = false: small_plan refuses them); nc_bwd_kernel has no <SHARED = false, EPI = true> (launch_bwd).
-template <int V> using ic = std::integral_constant<int, V>;
-template <class F> static void with_flag(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+// run-time value -> template argument, beside with_flag / with_dm of nc_shared.h.  Only what the kernels are instantiated for is
+// reachable: K-slices {1,2,3,4,8}; the one-launch kernels do not exist for explicit masks (with_dm<false>: small_plan refuses
+// them); nc_bwd_kernel has no <SHARED = false, EPI = true> (launch_bwd).
 template <class F> static void with_k(int Ks, F&& f) {
   switch (Ks) {
     case 1: f(ic<1>{}); break;
@@ -926,12 +883,6 @@ template <class F> static void with_k(int Ks, F&& f) {
     case 4: f(ic<4>{}); break;
     default: f(ic<8>{}); break;
   }
-}
-template <bool EXPLICIT_OK = true, class F> static void with_dm(int dm, F&& f) {
-  if (dm == MMA_DROP_HASH) f(ic<MMA_DROP_HASH>{});
-  else if (dm == MMA_DROP_HASH16) f(ic<MMA_DROP_HASH16>{});
-  else if (EXPLICIT_OK && dm == MMA_DROP_EXPLICIT) f(ic<EXPLICIT_OK ? MMA_DROP_EXPLICIT : MMA_DROP_NONE>{});
-  else f(ic<MMA_DROP_NONE>{});
 }
 // VEC (4 or 1) and MULTI (item part 1: the grouped items) of the item kernels
 template <class F> static void with_form(int vec, int part, F&& f) {
@@ -984,30 +935,11 @@ static bool small_plan(int32_t* sync, int K, const Geometry& g, int dm, int64_t 
 // K in 1..8 is issued as slices the kernels are instantiated for: 8 | 4+{1,2,3} | {1,2,3,4}
 static int next_slice(int remaining) { return remaining >= 8 ? 8 : (remaining >= 4 ? 4 : remaining); }
 
-static int64_t elementwise_grid(int64_t total) {
-  int64_t b = (total + kBlock - 1) / kBlock;
-  return b < 1 ? 1 : (b > kMaxGrid * 4 ? kMaxGrid * 4 : b);
-}
-
-// ---- what mma_nc_fused_fwd and mma_nc_fused_bwd share.  The three check helpers are the shared requirements in the order the entry
-// points have always made them: each entry point's own checks sit between them.
+// ---- what mma_nc_fused_fwd and mma_nc_fused_bwd share
 static int nc_common_checks(int64_t N, int64_t E, int32_t H, int32_t K) {
-  MMA_REQUIRE(N >= 0 && E >= 0 && N < (1LL << 31) && E < (1LL << 31), "N=%lld E=%lld out of int32 range", (long long)N, (long long)E);
+  if (int rc = nc_range_checks(N, E)) return rc;
   MMA_REQUIRE(H >= 1 && K >= 1 && K <= MMA_MAX_K, "H=%d K=%d unsupported (1<=K<=%d)", H, K, MMA_MAX_K);
   return 0;
-}
-static int nc_item_checks(int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs, const float* partial, int64_t n_slots) {
-  MMA_REQUIRE(n_items >= 0 && n_hubs >= 0 && n_slots >= 0 && n_items < (1LL << 31) && n_wave_items >= 0, "negative or oversize item counts");
-  MMA_REQUIRE(n_slots == 0 || (partial != nullptr && hubs != nullptr && n_hubs > 0), "hub slots without partial/hubs buffers");
-  return 0;
-}
-static int nc_item_alignment(const int32_t* items, const int32_t* hubs) {
-  MMA_REQUIRE(aligned16(items) && (hubs == nullptr || aligned16(hubs)), "items/hubs must be 16-byte aligned int32 quadruples");
-  return 0;
-}
-// items [0, n_wave_items): one per wavefront; items [n_wave_items, n_items): one per LPR-lane group (short segments)
-static int64_t nc_wave_items(int ipw, int64_t n_items, int64_t n_wave_items) {
-  return (ipw == 1 || n_wave_items > n_items) ? n_items : n_wave_items;
 }
 // the hub list and the ticket counter of the one-launch form
 template <class Params>
@@ -1101,7 +1033,7 @@ static int nc_fused_fwd(
   if (int rc = check_launch("nc_fwd_kernel")) return rc;
   if (n_hubs > 0) {
     const int per_row = (H + g.vec - 1) / g.vec;
-    const dim3 fg((unsigned)elementwise_grid(n_hubs * per_row));
+    const dim3 fg = elementwise_grid(n_hubs * per_row);
     const int4* hb = reinterpret_cast<const int4*>(hubs);
     with_flag(g.vec == 4, [&](auto v4) { with_flag(save, [&](auto sv) {
       hipLaunchKernelGGL((nc_fwd_finalize_kernel<decltype(v4)::value ? 4 : 1, decltype(sv)::value, TT>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);
@@ -1256,7 +1188,7 @@ static int nc_fused_bwd(
   if (int rc = check_launch("nc_bwd_kernel")) return rc;
   if (n_hubs > 0) {
     const int per_row = (H + geo.vec - 1) / geo.vec;
-    const dim3 fg((unsigned)elementwise_grid(n_hubs * (K + 1) * per_row));
+    const dim3 fg = elementwise_grid(n_hubs * (K + 1) * per_row);
     const int4* hb = reinterpret_cast<const int4*>(hubs);
     with_flag(geo.vec == 4, [&](auto v4) {
       hipLaunchKernelGGL((nc_bwd_finalize_kernel<decltype(v4)::value ? 4 : 1, TT>), fg, dim3(kBlock), 0, st, p, hb, n_hubs);

@@ -20,8 +20,7 @@
 // own P row and gathered Q rows, the backward's own Q row and gathered P rows; a value is widened with bits << 16, which is exact, so
 // everything behind the load - the fp64 sums, x, g r, mean, every gradient - is the fp32 code, and the backward recomputes z from
 // exactly what the forward read.
-#include <type_traits>
-#include "common.h"
+#include "nc_shared.h"
 
 namespace mma {
 
@@ -39,9 +38,6 @@ struct NcStdFwdParams {
   int H, lpr_log, raw;
   DropParams drop;
 };
-
-// row * pitch as ONE v_mad_u64_u32 (rows and pitches are < 2^31: checked on the host)
-__device__ __forceinline__ size_t std_row_off(int row, int64_t ld) { return (size_t)((uint64_t)(uint32_t)row * (uint64_t)(uint32_t)ld); }
 
 // keep factors of the VEC features at column c of edge e.  The std mask is mask 0 of a launch of its own: its HASH word is the base
 // word itself, its EXPLICIT mask is (1,E,H).
@@ -99,9 +95,9 @@ __device__ __forceinline__ void nc_std_write(const NcStdFwdParams<TT>& p, int no
       coef.v[i] = (float)(rr * (t2.v[i] - mn * t1.v[i]));
     }
   }
-  stv_nt<VEC>(p.m + std_row_off(node, p.ldm) + c, mo);
+  stv_nt<VEC>(p.m + row_off(node, p.ldm) + c, mo);
   if (SAVE) {
-    float* sv = p.saved + std_row_off(node, p.ldsv) + c;
+    float* sv = p.saved + row_off(node, p.ldsv) + c;
     stv<VEC>(sv, mean);                         // mean (and r, through g r) is re-read per edge by the backward: plain stores
     stv<VEC>(sv + p.H, r);
     stv_nt<VEC>(sv + 2 * (size_t)p.H, coef);
@@ -152,7 +148,7 @@ __global__ __launch_bounds__(kBlock, 2) void nc_std_fwd_kernel(const NcStdFwdPar
       maxlen = __builtin_amdgcn_readfirstlane(maxlen);
     }
 
-    const Vec<VEC> pi = ldt_nt<VEC>(p.P + std_row_off(node, p.ldp) + cc);
+    const Vec<VEC> pi = ldt_nt<VEC>(p.P + row_off(node, p.ldp) + cc);
     DVec<VEC> s1 = dzero<VEC>(), s2 = dzero<VEC>(), t1 = dzero<VEC>(), t2 = dzero<VEC>();
 
     for (int base = 0; base < maxlen; base += G) {
@@ -167,8 +163,8 @@ __global__ __launch_bounds__(kBlock, 2) void nc_std_fwd_kernel(const NcStdFwdPar
           ev[u] = tt[u] < cnt;
           const int j = __shfl(myj, gbase + (tt[u] & (G - 1)), kWave);
           const int jj = ev[u] ? j : node;     // inactive sub-rows re-read the item's own rows (cached); zeroed by the select below
-          xj[u] = ldv<VEC>(p.x + std_row_off(jj, p.ldx) + cc);
-          qv[u] = ldt<VEC>(p.Q + std_row_off(jj, p.ldq) + cc);
+          xj[u] = ldv<VEC>(p.x + row_off(jj, p.ldx) + cc);
+          qv[u] = ldt<VEC>(p.Q + row_off(jj, p.ldq) + cc);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -337,8 +333,8 @@ __global__ __launch_bounds__(kBlock, 2) void nc_std_bwd_kernel(const NcStdBwdPar
       maxlen = __builtin_amdgcn_readfirstlane(maxlen);
     }
 
-    const Vec<VEC> xj = ldv_nt<VEC>(p.x + std_row_off(node, p.ldx) + cc);
-    const Vec<VEC> qj = ldt_nt<VEC>(p.Q + std_row_off(node, p.ldq) + cc);
+    const Vec<VEC> xj = ldv_nt<VEC>(p.x + row_off(node, p.ldx) + cc);
+    const Vec<VEC> qj = ldt_nt<VEC>(p.Q + row_off(node, p.ldq) + cc);
     Vec<VEC> aq = vzero<VEC>(), ax = vzero<VEC>();
 
     for (int base = 0; base < maxlen; base += G) {
@@ -359,9 +355,9 @@ __global__ __launch_bounds__(kBlock, 2) void nc_std_bwd_kernel(const NcStdBwdPar
           const int tl = min(tt, max(cnt - 1, 0));
           const int ii = __shfl(myi, gbase + (tl & (G - 1)), kWave);
           eid[u] = DROP ? (uint32_t)__shfl(mye, gbase + (tl & (G - 1)), kWave) : 0u;
-          pv[u] = ldt<VEC>(p.P + std_row_off(ii, p.ldp) + cc);
-          gv[u] = ldv<VEC>(p.gr + std_row_off(ii, p.ldgr) + cc);
-          mv[u] = ldv<VEC>(p.mean + std_row_off(ii, p.ldsv) + cc);
+          pv[u] = ldt<VEC>(p.P + row_off(ii, p.ldp) + cc);
+          gv[u] = ldv<VEC>(p.gr + row_off(ii, p.ldgr) + cc);
+          mv[u] = ldv<VEC>(p.mean + row_off(ii, p.ldsv) + cc);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -400,8 +396,8 @@ __global__ __launch_bounds__(kBlock, 2) void nc_std_bwd_kernel(const NcStdBwdPar
         Vec<VEC> o;
 #pragma unroll
         for (int i = 0; i < VEC; ++i) o.v[i] = xj.v[i] * aq.v[i];
-        stv_nt<VEC>(p.gQ + std_row_off(node, p.ldgq) + c, o);
-        stv_nt<VEC>(p.gx + std_row_off(node, p.ldgx) + c, ax);
+        stv_nt<VEC>(p.gQ + row_off(node, p.ldgq) + c, o);
+        stv_nt<VEC>(p.gx + row_off(node, p.ldgx) + c, ax);
       } else {
         float* ps = p.partial + (size_t)slot * p.pstride + c;
         stv<VEC>(ps, aq);
@@ -426,22 +422,17 @@ __global__ __launch_bounds__(kBlock) void nc_std_bwd_finalize_kernel(const NcStd
       for (int i = 0; i < VEC; ++i) { aq.v[i] += a.v[i]; ax.v[i] += b.v[i]; }
     }
     const int node = hub.x;
-    const Vec<VEC> xj = ldv<VEC>(p.x + std_row_off(node, p.ldx) + c);
+    const Vec<VEC> xj = ldv<VEC>(p.x + row_off(node, p.ldx) + c);
     Vec<VEC> o;
 #pragma unroll
     for (int i = 0; i < VEC; ++i) o.v[i] = xj.v[i] * aq.v[i];
-    stv_nt<VEC>(p.gQ + std_row_off(node, p.ldgq) + c, o);
-    stv_nt<VEC>(p.gx + std_row_off(node, p.ldgx) + c, ax);
+    stv_nt<VEC>(p.gQ + row_off(node, p.ldgq) + c, o);
+    stv_nt<VEC>(p.gx + row_off(node, p.ldgx) + c, ax);
   }
 }
 
 // ------------------------------------------------------------------------------------------------------
-// host side: the checks, geometry and launch ladder of the NC entry points in nc_fused.hip, restated for one mask as file-static
-// copies because that file is left untouched here.  Follow-up: hoist nc_common_checks / nc_item_checks / nc_item_alignment, make_drop,
-// geometry, item_grid and elementwise_grid into common.h and have both files use them, so that the two copies cannot drift.
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-// a logit table's vector condition: one lane reads 4 elements at once - 16 bytes of fp32, 8 bytes of bf16
-template <class TT> static bool table_aligned(const TT* p) { return (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(TT) - 1)) == 0; }
+// host side: what is specific to K1s / K2s; the checks, make_drop, geometry, the grids and with_flag / with_dm are in nc_shared.h
 // a bf16 table at an odd address cannot be read at all (the scalar form loads 2-byte elements); fp32 tables are taken as they always were
 template <class TT> static int std_table_checks(const TT* P, const TT* Q) {
   MMA_REQUIRE(sizeof(TT) != 2 || ((reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(Q)) & 1u) == 0,
@@ -450,29 +441,8 @@ template <class TT> static int std_table_checks(const TT* P, const TT* Q) {
 }
 
 static int nc_common_checks(int64_t N, int64_t E, int32_t H) {
-  MMA_REQUIRE(N >= 0 && E >= 0 && N < (1LL << 31) && E < (1LL << 31), "N=%lld E=%lld out of int32 range", (long long)N, (long long)E);
+  if (int rc = nc_range_checks(N, E)) return rc;
   MMA_REQUIRE(H >= 1 && H < (1 << 28), "H=%d unsupported", H);
-  return 0;
-}
-static int nc_item_checks(int64_t n_items, int64_t n_wave_items, const int32_t* hubs, int64_t n_hubs, const void* partial, int64_t n_slots) {
-  MMA_REQUIRE(n_items >= 0 && n_hubs >= 0 && n_slots >= 0 && n_items < (1LL << 31) && n_wave_items >= 0, "negative or oversize item counts");
-  MMA_REQUIRE(n_slots == 0 || (partial != nullptr && hubs != nullptr && n_hubs > 0), "hub slots without partial/hubs buffers");
-  return 0;
-}
-static int nc_item_alignment(const int32_t* items, const int32_t* hubs) {
-  MMA_REQUIRE(aligned16(items) && (hubs == nullptr || aligned16(hubs)), "items/hubs must be 16-byte aligned int32 quadruples");
-  return 0;
-}
-static int std_make_drop(int32_t mode, uint32_t thr, uint64_t seed, const uint64_t* seed_dev, int64_t edge_base, const uint8_t* keep,
-                         int64_t E, DropParams* d) {
-  d->seed_dev = seed_dev;
-  MMA_REQUIRE(edge_base >= 0 && edge_base < (1LL << 32) && edge_base + E < (1LL << 32), "drop_edge_base %lld out of range", (long long)edge_base);
-  d->edge_base = (uint32_t)edge_base;
-  MMA_REQUIRE(mode >= MMA_DROP_NONE && mode <= MMA_DROP_EXPLICIT, "drop_mode %d unknown", mode);
-  MMA_REQUIRE(mode == MMA_DROP_NONE || thr < 65536, "drop_thr %u out of range (0..65535: P(drop) = thr / 65536)", thr);
-  MMA_REQUIRE(mode != MMA_DROP_EXPLICIT || keep != nullptr, "drop_mode EXPLICIT needs a keep mask");
-  drop_set_threshold(d, mode, thr);
-  d->seed_lo = (uint32_t)seed; d->seed_hi = (uint32_t)(seed >> 32); d->keep = keep; d->E = E;
   return 0;
 }
 // the kernels' dropout form: HASH with threshold 0 drops nothing, and so does any mode on a graph without edges
@@ -480,42 +450,11 @@ static int std_drop_form(int32_t mode, uint32_t thr, int64_t E, const DropParams
   return ((mode == MMA_DROP_HASH && thr == 0) || E == 0) ? MMA_DROP_NONE : d.mode;
 }
 
-struct StdGeometry { int vec, lpr_log, chunks; };
-// lanes per row: next power of two >= ceil(H/vec), at most one wave; wider rows take gridDim.y chunks
-static StdGeometry std_geometry(int H, bool vec4_ok) {
-  StdGeometry g;
-  g.vec = vec4_ok ? 4 : 1;
-  const int per_row = (H + g.vec - 1) / g.vec;
-  g.lpr_log = min(ilog2_ceil(per_row), 6);
-  g.chunks = (per_row + (1 << g.lpr_log) - 1) >> g.lpr_log;
-  return g;
-}
-static dim3 item_grid(int64_t n_items, int chunks, int items_per_wave) {
-  const int64_t per_block = (int64_t)(kBlock / kWave) * items_per_wave;
-  int64_t blocks = (n_items + per_block - 1) / per_block;
-  if (blocks > kMaxGrid) blocks = kMaxGrid;
-  if (blocks < 1) blocks = 1;
-  return dim3((unsigned)blocks, (unsigned)chunks, 1);
-}
-static dim3 elementwise_grid(int64_t total) {
-  int64_t b = (total + kBlock - 1) / kBlock;
-  return dim3((unsigned)(b < 1 ? 1 : (b > kMaxGrid * 4 ? kMaxGrid * 4 : b)));
-}
-
-// run-time value -> template argument (a generic lambda reads decltype(v)::value)
-template <int V> using ic = std::integral_constant<int, V>;
-template <class F> static void with_flag(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
-template <class F> static void with_dm(int dm, F&& f) {
-  if (dm == MMA_DROP_HASH) f(ic<MMA_DROP_HASH>{});
-  else if (dm == MMA_DROP_HASH16) f(ic<MMA_DROP_HASH16>{});
-  else if (dm == MMA_DROP_EXPLICIT) f(ic<MMA_DROP_EXPLICIT>{});
-  else f(ic<MMA_DROP_NONE>{});
-}
 // the two item launches: items [0, n_wave_items) one per wavefront, the rest one per LPR-lane group.  f(items, count, multi, grid)
 template <class F>
-static void std_for_parts(const int32_t* items, int64_t n_items, int64_t n_wave_items, const StdGeometry& g, F&& f) {
+static void std_for_parts(const int32_t* items, int64_t n_items, int64_t n_wave_items, const Geometry& g, F&& f) {
   const int ipw = kWave >> g.lpr_log;
-  if (ipw == 1 || n_wave_items > n_items) n_wave_items = n_items;
+  n_wave_items = nc_wave_items(ipw, n_items, n_wave_items);
   const int4* all = reinterpret_cast<const int4*>(items);
   if (n_wave_items > 0) f(all, n_wave_items, false, item_grid(n_wave_items, g.chunks, 1));
   if (n_items > n_wave_items) f(all + n_wave_items, n_items - n_wave_items, true, item_grid(n_items - n_wave_items, g.chunks, ipw));
@@ -551,13 +490,13 @@ static int nc_std_fwd(
   if (int rc = nc_item_alignment(items, hubs)) return rc;
   MMA_REQUIRE((reinterpret_cast<uintptr_t>(partial) & 7u) == 0, "partial must be 8-byte aligned (fp64 sums)");
   NcStdFwdParams<TT> p{};
-  if (int rc = std_make_drop(drop_mode, drop_thr, seed, seed_dev, drop_edge_base, keep, E, &p.drop)) return rc;
+  if (int rc = make_drop(drop_mode, drop_thr, seed, seed_dev, drop_edge_base, keep, E, &p.drop)) return rc;
   const int dm = std_drop_form(drop_mode, drop_thr, E, p.drop);
   const bool save = saved != nullptr;
   const bool v4 = (H % 4 == 0) && (ldx % 4 == 0) && (ldp % 4 == 0) && (ldq % 4 == 0) && (ldms % 4 == 0) && (!save || ldt % 4 == 0) &&
                   aligned16(x) && table_aligned(P) && table_aligned(Q) && aligned16(m) && (!save || aligned16(saved)) &&
                   (partial == nullptr || aligned16(partial));
-  const StdGeometry g = std_geometry(H, v4);
+  const Geometry g = geometry(H, v4);
   p.x = x; p.ldx = ldx; p.P = P; p.ldp = ldp; p.Q = Q; p.ldq = ldq; p.rowptr = rowptr; p.col = col;
   p.partial = partial; p.pstride = (save ? 4LL : 2LL) * H;
   p.m = m; p.ldm = ldms; p.saved = saved; p.ldsv = ldt;
@@ -610,12 +549,12 @@ static int nc_std_bwd(
   if (int rc = std_table_checks(P, Q)) return rc;
   if (int rc = nc_item_alignment(items, hubs)) return rc;
   NcStdBwdParams<TT> p{};
-  if (int rc = std_make_drop(drop_mode, drop_thr, seed, seed_dev, drop_edge_base, keep, E, &p.drop)) return rc;
+  if (int rc = make_drop(drop_mode, drop_thr, seed, seed_dev, drop_edge_base, keep, E, &p.drop)) return rc;
   const int dm = std_drop_form(drop_mode, drop_thr, E, p.drop);
   const bool v4 = (H % 4 == 0) && (ldx % 4 == 0) && (ldp % 4 == 0) && (ldq % 4 == 0) && (ldg % 4 == 0) && (ldt % 4 == 0) && (ldgr % 4 == 0) &&
                   (ldgp % 4 == 0) && (ldgq % 4 == 0) && (ldgx % 4 == 0) && aligned16(x) && table_aligned(P) && table_aligned(Q) && aligned16(g) &&
                   aligned16(saved) && aligned16(gr) && aligned16(gP) && aligned16(gQ) && aligned16(gx) && (partial == nullptr || aligned16(partial));
-  const StdGeometry geo = std_geometry(H, v4);
+  const Geometry geo = geometry(H, v4);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int per_row = (H + geo.vec - 1) / geo.vec;
   {

@@ -12,38 +12,29 @@ bits.  The layer tests assert this (the saved bf16 table equals the oracle's bit
 rounding itself moves the logits by up to 2^-9 |z| ~ 1e-3, every sum runs over inexact fp32 terms, and the bar follows the data.
 The gradient passes the rounding straight through, on both sides.
 
-Shapes are the smallest at which the kernels take another path (see tests/test_nc_std_gpu.py, whose graphs these are)."""
+Shapes are the smallest at which the kernels take another path (the graphs of tests/nc_layer_util.py).  This file's own defaults: bf16
+tables, the weights on the 2^-9 grid, x on the 2^-5 grid."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 from golden_util import check_close
 from golden.inputs import ALL_MASK_NAMES
+from nc_layer_util import (BF16, BOUNDARY as _BOUNDARY, C_OUT, DEV, HUB as _HUB, SMALL as _SMALL, csr_of, normalized_adj, rounded,
+                           small_graph_with_a_hub)
+import nc_layer_util
 from oracle import nc_oracle as O
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-C_OUT = 4
 FIVE = ["sum", "mean3", "max", "min", "softmax"]
 EIGHT = ["sum", "mean", "max", "min", "softmax", "softmin", "sum2", "mean3"]
-BF16 = torch.bfloat16
+_SMALL_HUB = small_graph_with_a_hub()
+make_layer = functools.partial(nc_layer_util.make_layer, logit_dtype=BF16, grid=True)
 
 
 # ---- the definition, in torch (any dtype, CPU) ---------------------------------------------------------------------------------
-def csr_of(add_all):
-    deg = np.array([len(a) for a in add_all], dtype=np.int64)
-    col = np.concatenate([np.asarray(a, dtype=np.int64) for a in add_all]) if deg.sum() else np.zeros(0, np.int64)
-    return deg, col
-
-
-def rounded(t, table_dtype):
-    """The stored table: t rounded to bf16 and widened again; the gradient passes straight through (r - t is exact, t + (r - t) = r)."""
-    if table_dtype == torch.float32:
-        return t
-    r = t.detach().to(torch.bfloat16).to(t.dtype)
-    return t + (r - t.detach())
-
-
 def fused_oracle(x, Ws, names, add_all, activation, keeps=None, p=0.0, table_dtype=BF16):
     """m (K,N,H): the fused aggregators `names` with mask weights Ws[k] (2H,H); keeps: (K,E,H) 0/1 or None."""
     N, H = x.shape
@@ -73,88 +64,6 @@ def oracle_with_grads(x, Ws, names, add_all, activation, cot, cot_k, keeps=None,
     gk = torch.autograd.grad((m * cot_k.to(dtype)).sum(), [xo] + Wo)
     n = lambda t: t.detach().numpy()
     return {"m": n(m), "msum": n(m.sum(0)), "gx": n(gs[0]), "gmask": [n(g) for g in gs[1:]], "gx_k": n(gk[0]), "gmask_k": [n(g) for g in gk[1:]]}
-
-
-# ---- graphs (tests/test_nc_std_gpu.py) -------------------------------------------------------------------------------------------
-BOUNDARY_DEGREES = [0, 1, 2, 7, 8, 9, 63, 64, 65]
-
-
-def boundary_graph():
-    rng = np.random.default_rng(7)
-    N = 120
-    edges = set()
-    for t, d in enumerate(BOUNDARY_DEGREES):
-        for s in rng.choice(np.arange(19, N), size=d, replace=False):
-            edges.add((t, int(s)))
-    for k, d in enumerate(BOUNDARY_DEGREES):
-        for t in rng.choice(np.arange(20, N), size=d, replace=False):
-            edges.add((int(t), 10 + k))
-    for t in range(20, N):
-        for s in rng.choice(np.arange(19, N), size=rng.integers(0, 6), replace=False):
-            edges.add((t, int(s)))
-    add_all = [sorted(s for (t, s) in edges if t == i) for i in range(N)]
-    assert [len(add_all[t]) for t in range(9)] == BOUNDARY_DEGREES
-    return add_all
-
-
-def hub_graph():
-    rng = np.random.default_rng(11)
-    N = 300
-    edges = {(0, s) for s in range(60, 260)} | {(t, 1) for t in range(80, 280)}
-    for t in range(2, N):
-        for s in rng.choice(np.arange(2, N), size=rng.integers(0, 5), replace=False):
-            edges.add((t, int(s)))
-    return [sorted(s for (t, s) in edges if t == i) for i in range(N)]
-
-
-def small_graph(N=150, seed=9):
-    rng = np.random.default_rng(seed)
-    return [sorted(rng.choice(N, size=rng.integers(0, 8), replace=False).tolist()) for _ in range(N)]
-
-
-def normalized_adj(add_all):
-    N = len(add_all)
-    A = np.eye(N)
-    for i, a in enumerate(add_all):
-        A[i, a] = 1.0
-    A /= A.sum(1, keepdims=True)
-    idx = np.nonzero(A)
-    sp = torch.sparse_coo_tensor(torch.from_numpy(np.stack(idx)), torch.from_numpy(A[idx].astype(np.float32)), (N, N))
-    return torch.from_numpy(A), sp.to(DEV)
-
-
-_BOUNDARY = boundary_graph()
-_HUB = hub_graph()
-_SMALL = small_graph()
-
-
-def small_graph_with_a_hub():
-    """_SMALL plus one target with 40 neighbours and one source with 40 out-edges: items per wavefront, items per lane group and, with
-    chunk=32, one hub in two partial slots each way - the plan the one-launch form takes with its ticket counter."""
-    add_all = [list(a) for a in _SMALL]
-    add_all[0] = list(range(10, 50))
-    for t in range(60, 100):
-        add_all[t] = sorted(set(add_all[t]) | {1})
-    return add_all
-
-
-_SMALL_HUB = small_graph_with_a_hub()
-
-
-# ---- the layer -------------------------------------------------------------------------------------------------------------------
-def make_layer(add_all, H, aggs, activation="sigmoid", p=0.0, chunk=None, seed=0, scale=1.0, **kw):
-    import mma_amd
-    torch.manual_seed(seed)
-    P = lambda *s: torch.nn.Parameter(torch.empty(*s, device=DEV))
-    masks = [P(2 * H, H) for _ in ALL_MASK_NAMES]
-    kw.setdefault("logit_dtype", BF16)
-    if chunk is not None:
-        kw["chunk"] = chunk
-    layer = mma_amd.MMA(add_all, activation, 2, H, C_OUT, P(H, C_OUT), P(C_OUT), *masks, p, list(aggs), DEV, **kw)     # reset_parameters draws
-    with torch.no_grad():
-        for w in masks:                                   # the 2^-9 grid (module docstring); `scale`: a power of two
-            w.copy_(torch.round(w * 512.0) / 512.0 * scale)
-    return layer
 
 
 def inputs(add_all, H, K, seed=3):

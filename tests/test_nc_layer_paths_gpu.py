@@ -64,7 +64,7 @@ def slices_of(K):
 
 
 def geometry(H):
-    """(vec, lpr_log, chunks, items per wavefront) as `geometry()` in nc_fused.hip picks them for the buffers of the layer."""
+    """(vec, lpr_log, chunks, items per wavefront) as `geometry()` in nc_shared.h picks them for the buffers of the layer."""
     vec = 4 if H % 4 == 0 else 1
     per_row = -(-H // vec)
     lpr_log = min((per_row - 1).bit_length(), 6)

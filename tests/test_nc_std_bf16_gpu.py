@@ -1,6 +1,6 @@
 """GPU tests of the bf16 logit tables of the `std` aggregator (MMA(..., strict_reference=False, logit_dtype=torch.bfloat16);
 include/mma_amd.h ABI 40: mma_nc_std_fwd_h / mma_nc_std_bwd_h, csrc/nc_moments.hip) against the plain torch statement of the aggregator
-(tests/test_nc_std_gpu.py: std_oracle) in which P and Q are rounded with .to(torch.bfloat16).to(dtype) before z = P[dst] + Q[col].
+(tests/nc_layer_util.py: std_oracle) in which P and Q are rounded with .to(torch.bfloat16).to(dtype) before z = P[dst] + Q[col].
 float64 on the CPU is the truth, the same statement in float32 the reference value, and the bar is the project's own, unchanged
 (golden_util.check_close with truth).
 
@@ -10,165 +10,34 @@ within +-1/sqrt(H) - a sum of H <= 128 products is a multiple of 2^-14 below 2^6
 order and in the split-fp16 GEMMs.  The layer test asserts it (the saved bf16 table equals the oracle's bit for bit).  The gradient
 passes the rounding straight through, on both sides.
 
-Graphs and shapes are those of tests/test_nc_std_gpu.py (restated): degrees around the group / wavefront item split and the 64-index
-chunk, a hub cut into partial slots both ways, H = 8 / 20 / 128 (8-byte table vectors; 20: a partial lane group) and H = 6 (scalar
-2-byte loads)."""
+Graphs and shapes are those of tests/test_nc_std_gpu.py (tests/nc_layer_util.py): degrees around the group / wavefront item split and
+the 64-index chunk, a hub cut into partial slots both ways, H = 8 / 20 / 128 (8-byte table vectors; 20: a partial lane group) and H = 6 (scalar
+2-byte loads).  This file's own defaults: bf16 tables, the weights on the 2^-9 grid, x on the 2^-5 grid."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 from golden_util import check_close
 from golden.inputs import ALL_MASK_NAMES
+from nc_layer_util import BF16, BOUNDARY as _BOUNDARY, C_OUT, DEV, HUB as _HUB, SMALL as _SMALL, csr_of, normalized_adj, rounded, run_std
+import nc_layer_util
 from oracle import nc_oracle as O
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-C_OUT = 4
-BF16 = torch.bfloat16
 F32 = torch.float32
-
-
-# ---- the definition, in torch (any dtype, CPU) ---------------------------------------------------------------------------------
-def csr_of(add_all):
-    deg = np.array([len(a) for a in add_all], dtype=np.int64)
-    col = np.concatenate([np.asarray(a, dtype=np.int64) for a in add_all]) if deg.sum() else np.zeros(0, np.int64)
-    return deg, col
-
-
-def rounded(t, table_dtype):
-    """The stored table: t rounded to bf16 and widened again; the gradient passes straight through (r - t is exact, t + (r - t) = r)."""
-    if table_dtype == torch.float32:
-        return t
-    r = t.detach().to(torch.bfloat16).to(t.dtype)
-    return t + (r - t.detach())
-
-
-def std_oracle(x, W, add_all, activation, keep=None, p=0.0, table_dtype=BF16):
-    """m (N,H) = sqrt(relu(msq - mean^2) + 1e-5) of the masked neighbour messages; keep: (E,H) 0/1 or None."""
-    N, H = x.shape
-    deg, col = csr_of(add_all)
-    dst = torch.from_numpy(np.repeat(np.arange(N), deg))
-    col = torch.from_numpy(col)
-    P, Q = rounded(x @ W[:H], table_dtype), rounded(x @ W[H:], table_dtype)
-    z = P[dst] + Q[col]
-    a = z if activation == "new_sigmoid" else torch.sigmoid(z)
-    mu = a * x[col]
-    if keep is not None:
-        mu = (keep.to(x.dtype) / (1.0 - p)) * mu
-    d = torch.from_numpy(np.maximum(deg, 1)).to(x.dtype).unsqueeze(1)
-    mean = torch.zeros(N, H, dtype=x.dtype).index_add(0, dst, mu) / d
-    msq = torch.zeros(N, H, dtype=x.dtype).index_add(0, dst, mu * mu) / d
-    return torch.sqrt(torch.relu(msq - mean * mean) + 1e-5)
-
-
-def oracle_with_grads(x, W, add_all, activation, cot, keep=None, p=0.0, dtype=torch.float64, table_dtype=BF16):
-    xo = x.to(dtype).requires_grad_(True)
-    Wo = W.to(dtype).requires_grad_(True)
-    m = std_oracle(xo, Wo, add_all, activation, keep, p, table_dtype)
-    gx, gW = torch.autograd.grad((m * cot.to(dtype)).sum(), [xo, Wo])
-    return m.detach().numpy(), gx.numpy(), gW.numpy()
-
-
-# ---- graphs (tests/test_nc_std_gpu.py) -------------------------------------------------------------------------------------------
-BOUNDARY_DEGREES = [0, 1, 2, 7, 8, 9, 63, 64, 65]
-
-
-def boundary_graph():
-    rng = np.random.default_rng(7)
-    N = 120
-    edges = set()
-    for t, d in enumerate(BOUNDARY_DEGREES):
-        for s in rng.choice(np.arange(19, N), size=d, replace=False):
-            edges.add((t, int(s)))
-    for k, d in enumerate(BOUNDARY_DEGREES):
-        for t in rng.choice(np.arange(20, N), size=d, replace=False):
-            edges.add((int(t), 10 + k))
-    for t in range(20, N):
-        for s in rng.choice(np.arange(19, N), size=rng.integers(0, 6), replace=False):
-            edges.add((t, int(s)))
-    add_all = [sorted(s for (t, s) in edges if t == i) for i in range(N)]
-    assert [len(add_all[t]) for t in range(9)] == BOUNDARY_DEGREES
-    return add_all
-
-
-def hub_graph():
-    rng = np.random.default_rng(11)
-    N = 300
-    edges = {(0, s) for s in range(60, 260)} | {(t, 1) for t in range(80, 280)}
-    for t in range(2, N):
-        for s in rng.choice(np.arange(2, N), size=rng.integers(0, 5), replace=False):
-            edges.add((t, int(s)))
-    return [sorted(s for (t, s) in edges if t == i) for i in range(N)]
-
-
-def small_graph(N=150, seed=9):
-    rng = np.random.default_rng(seed)
-    return [sorted(rng.choice(N, size=rng.integers(0, 8), replace=False).tolist()) for _ in range(N)]
-
-
-def normalized_adj(add_all):
-    N = len(add_all)
-    A = np.eye(N)
-    for i, a in enumerate(add_all):
-        A[i, a] = 1.0
-    A /= A.sum(1, keepdims=True)
-    idx = np.nonzero(A)
-    sp = torch.sparse_coo_tensor(torch.from_numpy(np.stack(idx)), torch.from_numpy(A[idx].astype(np.float32)), (N, N))
-    return torch.from_numpy(A), sp.to(DEV)
-
-
-def degenerate_targets(add_all):
-    """Targets whose exact variance is 0 by construction: degree 0, degree 1, all edges from one source."""
-    return [i for i, a in enumerate(add_all) if len(a) <= 1 or len(set(a)) == 1]
-
-
-_BOUNDARY = boundary_graph()
-_HUB = hub_graph()
-_SMALL = small_graph()
-
-
-# ---- the layer -------------------------------------------------------------------------------------------------------------------
-def make_layer(add_all, H, aggs, activation="sigmoid", p=0.0, chunk=None, seed=0, scale=1.0, **kw):
-    import mma_amd
-    torch.manual_seed(seed)
-    P = lambda *s: torch.nn.Parameter(torch.empty(*s, device=DEV))
-    masks = [P(2 * H, H) for _ in ALL_MASK_NAMES]
-    kw.setdefault("logit_dtype", BF16)
-    kw.setdefault("strict_reference", False)
-    if chunk is not None:
-        kw["chunk"] = chunk
-    layer = mma_amd.MMA(add_all, activation, 2, H, C_OUT, P(H, C_OUT), P(C_OUT), *masks, p, list(aggs), DEV, **kw)     # reset_parameters draws
-    with torch.no_grad():
-        for w in masks:                                   # the 2^-9 grid (module docstring); `scale`: a power of two
-            w.copy_(torch.round(w * 512.0) / 512.0 * scale)
-    return layer
-
-
-def inputs(add_all, H, seed=3):
-    rng = np.random.default_rng(seed)
-    N = len(add_all)
-    x = torch.from_numpy((rng.integers(-32, 33, (N, H)) / 32.0).astype(np.float32))          # the 2^-5 grid
-    cot = torch.from_numpy(rng.standard_normal((N, H)).astype(np.float32))
-    cot[degenerate_targets(add_all)] = 0        # exact variance 0: relu' decides the gradient there (tests/test_nc_std_gpu.py checks it by construction)
-    return x, cot
-
-
-def run_std(layer, x, cot):
-    """(m, gx, gmask_std) of layer.learnable_std on the GPU."""
-    xg = x.to(DEV).requires_grad_(True)
-    m = layer.learnable_std(xg, None)
-    gx, gw = torch.autograd.grad((m * cot.to(DEV)).sum(), [xg, layer.mask_std])
-    torch.cuda.synchronize()
-    return m.detach(), gx, gw
-
-
+std_oracle = functools.partial(nc_layer_util.std_oracle, table_dtype=BF16)
+oracle_with_grads = functools.partial(nc_layer_util.oracle_with_grads, table_dtype=BF16)
+make_layer = functools.partial(nc_layer_util.make_layer, logit_dtype=BF16, strict_reference=False, grid=True)
+inputs = functools.partial(nc_layer_util.std_inputs, x_grid=True)
 _ORACLE = {}
 
 
 def oracles(key, x, W, add_all, activation, cot, keep=None, p=0.0, table_dtype=BF16):
     """(float32 reference, float64 truth) of (m, gx, gmask_std), computed once per `key` and shared by the tests that need them."""
     if key not in _ORACLE:
-        _ORACLE[key] = tuple(oracle_with_grads(x, W, add_all, activation, cot, keep, p, dt, table_dtype) for dt in (torch.float32, torch.float64))
+        _ORACLE[key] = tuple(oracle_with_grads(x, W, add_all, activation, cot, keep, p, dt, table_dtype=table_dtype) for dt in (torch.float32, torch.float64))
     return _ORACLE[key]
 
 

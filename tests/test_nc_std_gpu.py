@@ -3,8 +3,10 @@ restatement of its definition (mma_amd/layers.py docstring, DESIGN.md "std aggre
 statement in float32 on the CPU the reference value, and the bar is the project's own (golden_util.check_close with truth:
 1e-5 + 1e-5|ref| + 6 x the row noise of the fp32 reference).  Compared: m, dL/dx and dL/dmask_std.
 
-Shapes are the smallest at which the kernels take another path: degrees around the group / wavefront item split and the 64-index
-chunk, a hub cut into partial slots (forward and transposed), H = 8 / 20 / 128 and one H that is no multiple of 4."""
+Shapes are the smallest at which the kernels take another path: the graphs of tests/nc_layer_util.py (degrees around the group /
+wavefront item split and the 64-index chunk, a hub cut into partial slots, forward and transposed), H = 8 / 20 / 128 and one H that
+is no multiple of 4.  This file's own defaults: fp32 tables, the weights as drawn, x uniform in [-1, 1]."""
+import functools
 import math
 
 import numpy as np
@@ -12,116 +14,13 @@ import pytest
 import torch
 
 from golden_util import check_close
-from golden.inputs import ALL_MASK_NAMES
+from nc_layer_util import (BOUNDARY as _BOUNDARY, C_OUT, DEV, HUB as _HUB, degenerate_targets, normalized_adj, oracle_with_grads, run_std,
+                           small_graph, std_inputs as inputs, std_oracle)
+import nc_layer_util
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-C_OUT = 4
 SQRT_EPS = math.sqrt(1e-5)
-
-
-# ---- the definition, in torch (any dtype, CPU) ---------------------------------------------------------------------------------
-def csr_of(add_all):
-    deg = np.array([len(a) for a in add_all], dtype=np.int64)
-    col = np.concatenate([np.asarray(a, dtype=np.int64) for a in add_all]) if deg.sum() else np.zeros(0, np.int64)
-    return deg, col
-
-
-def std_oracle(x, W, add_all, activation, keep=None, p=0.0):
-    """m (N,H) = sqrt(relu(msq - mean^2) + 1e-5) of the masked neighbour messages; keep: (E,H) 0/1 or None."""
-    N, H = x.shape
-    deg, col = csr_of(add_all)
-    dst = torch.from_numpy(np.repeat(np.arange(N), deg))
-    col = torch.from_numpy(col)
-    P, Q = x @ W[:H], x @ W[H:]
-    z = P[dst] + Q[col]
-    a = z if activation == "new_sigmoid" else torch.sigmoid(z)
-    mu = a * x[col]
-    if keep is not None:
-        mu = (keep.to(x.dtype) / (1.0 - p)) * mu
-    d = torch.from_numpy(np.maximum(deg, 1)).to(x.dtype).unsqueeze(1)
-    mean = torch.zeros(N, H, dtype=x.dtype).index_add(0, dst, mu) / d
-    msq = torch.zeros(N, H, dtype=x.dtype).index_add(0, dst, mu * mu) / d
-    return torch.sqrt(torch.relu(msq - mean * mean) + 1e-5)
-
-
-def oracle_with_grads(x, W, add_all, activation, cot, keep=None, p=0.0, dtype=torch.float64):
-    xo = x.to(dtype).requires_grad_(True)
-    Wo = W.to(dtype).requires_grad_(True)
-    m = std_oracle(xo, Wo, add_all, activation, keep, p)
-    gx, gW = torch.autograd.grad((m * cot.to(dtype)).sum(), [xo, Wo])
-    return m.detach().numpy(), gx.numpy(), gW.numpy()
-
-
-# ---- graphs --------------------------------------------------------------------------------------------------------------------
-BOUNDARY_DEGREES = [0, 1, 2, 7, 8, 9, 63, 64, 65]      # MMA_SMALL_GROUP = 8: group / wavefront items; 64: one index chunk of a wavefront
-
-
-def boundary_graph():
-    """N = 120.  Targets 0..8 have the boundary in-degrees (distinct sources), sources 10..18 the same OUT-degrees (distinct targets
-    among 20..119): the transposed lists meet the same boundaries.  The other targets get 0..5 random neighbours."""
-    rng = np.random.default_rng(7)
-    N = 120
-    edges = set()
-    for t, d in enumerate(BOUNDARY_DEGREES):
-        for s in rng.choice(np.arange(19, N), size=d, replace=False):
-            edges.add((t, int(s)))
-    for k, d in enumerate(BOUNDARY_DEGREES):
-        for t in rng.choice(np.arange(20, N), size=d, replace=False):
-            edges.add((int(t), 10 + k))
-    for t in range(20, N):
-        for s in rng.choice(np.arange(19, N), size=rng.integers(0, 6), replace=False):
-            edges.add((t, int(s)))
-    add_all = [sorted(s for (t, s) in edges if t == i) for i in range(N)]
-    assert [len(add_all[t]) for t in range(9)] == BOUNDARY_DEGREES
-    return add_all
-
-
-def hub_graph():
-    """N = 300: target 0 has 200 distinct neighbours, source 1 has 200 out-edges; everything else 0..4 neighbours."""
-    rng = np.random.default_rng(11)
-    N = 300
-    edges = {(0, s) for s in range(60, 260)} | {(t, 1) for t in range(80, 280)}
-    for t in range(2, N):
-        for s in rng.choice(np.arange(2, N), size=rng.integers(0, 5), replace=False):
-            edges.add((t, int(s)))
-    return [sorted(s for (t, s) in edges if t == i) for i in range(N)]
-
-
-def degenerate_targets(add_all):
-    """Targets whose exact variance is 0 by construction: degree 0, degree 1, all edges from one source."""
-    return [i for i, a in enumerate(add_all) if len(a) <= 1 or len(set(a)) == 1]
-
-
-# ---- the layer -------------------------------------------------------------------------------------------------------------------
-def make_layer(add_all, H, aggs, activation="sigmoid", p=0.0, chunk=None, seed=0, **kw):
-    import mma_amd
-    torch.manual_seed(seed)
-    P = lambda *s: torch.nn.Parameter(torch.empty(*s, device=DEV))
-    masks = [P(2 * H, H) for _ in ALL_MASK_NAMES]
-    kw.setdefault("strict_reference", False)
-    if chunk is not None:
-        kw["chunk"] = chunk
-    return mma_amd.MMA(add_all, activation, 2, H, C_OUT, P(H, C_OUT), P(C_OUT), *masks, p, list(aggs), DEV, **kw)     # reset_parameters draws
-
-
-def inputs(add_all, H, seed=3):
-    rng = np.random.default_rng(seed)
-    N = len(add_all)
-    x = torch.from_numpy(rng.uniform(-1, 1, (N, H)).astype(np.float32))
-    cot = torch.from_numpy(rng.standard_normal((N, H)).astype(np.float32))
-    cot[degenerate_targets(add_all)] = 0        # their gradient is checked by construction (test_degenerate_variance), not by parity
-    return x, cot
-
-
-def run_std(layer, x, cot):
-    """(m, gx, gmask_std) of layer.learnable_std on the GPU."""
-    xg = x.to(DEV).requires_grad_(True)
-    layer.mask_std.grad = None
-    m = layer.learnable_std(xg, None)
-    gx, gw = torch.autograd.grad((m * cot.to(DEV)).sum(), [xg, layer.mask_std])
-    torch.cuda.synchronize()
-    return m.detach(), gx, gw
+make_layer = functools.partial(nc_layer_util.make_layer, strict_reference=False)
 
 
 def compare(got, x, W, add_all, activation, cot, what, keep=None, p=0.0):
@@ -131,10 +30,6 @@ def compare(got, x, W, add_all, activation, cot, what, keep=None, p=0.0):
         err = np.abs(g.detach().cpu().numpy().astype(np.float64) - t)
         print("%s/%s: max |got - fp64| %.3g, max |fp32 ref - fp64| %.3g" % (what, name, err.max(), np.abs(w.astype(np.float64) - t).max()))
         check_close(g, w, None, None, what=what + "/" + name, signed_sum=True, truth=t)
-
-
-_BOUNDARY = boundary_graph()
-_HUB = hub_graph()
 
 
 # ---- 1 + 3: item boundaries x widths x activations ---------------------------------------------------------------------------------
@@ -287,23 +182,6 @@ def test_degenerate_variance(H):
 
 
 # ---- 6: through the layer -----------------------------------------------------------------------------------------------------------------
-def small_graph(N=150, seed=9):
-    rng = np.random.default_rng(seed)
-    return [sorted(rng.choice(N, size=rng.integers(0, 8), replace=False).tolist()) for _ in range(N)]
-
-
-def normalized_adj(add_all):
-    """D^-1 (A + I), the adjacency the reference's training script hands to forward (utils.py normalize): dense float64 and sparse."""
-    N = len(add_all)
-    A = np.eye(N)
-    for i, a in enumerate(add_all):
-        A[i, a] = 1.0
-    A /= A.sum(1, keepdims=True)
-    idx = np.nonzero(A)
-    sp = torch.sparse_coo_tensor(torch.from_numpy(np.stack(idx)), torch.from_numpy(A[idx].astype(np.float32)), (N, N))
-    return torch.from_numpy(A), sp.to(DEV)
-
-
 def test_layer_forward_adds_the_std_tail():
     H = 20
     add_all = small_graph()

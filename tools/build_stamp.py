@@ -5,7 +5,7 @@ stamp differs from the running tree's (round-2 VERDICT item 8: a traffic figure 
 
 Round 4: kernel traffic also depends on the host-side planners and switches, and a stale .so must not pass.  The stamp is
   abi_version  include/mma_amd.h
-  kernel_sha   the SHA-256 over the kernel sources (mma_amd/csrc/*.hip, common.h, the header) EMBEDDED IN THE LOADED .so at build
+  kernel_sha   the SHA-256 over the kernel sources (mma_amd/csrc/*.hip, common.h, nc_shared.h, the header) EMBEDDED IN THE LOADED .so at build
                time (csrc/Makefile writes build_stamp.h from `--kernel-sha`; libmma_amd.so returns it from mma_build_stamp()); when
                no library is loadable the tree's own value is used and `library` says so
   host_sha     SHA-256 over the Python planners whose choices change what the kernels move (graph.py: chunking / grouping,
@@ -36,8 +36,9 @@ def _sha(files):
 
 
 def kernel_source_sha():
-    hdr = os.path.join(ROOT, "include", "mma_amd.h")
-    return _sha(sorted(glob.glob(os.path.join(ROOT, "mma_amd", "csrc", "*.hip"))) + [os.path.join(ROOT, "mma_amd", "csrc", "common.h"), hdr])
+    csrc = os.path.join(ROOT, "mma_amd", "csrc")       # its headers by name: the generated build_stamp.h sits there too
+    return _sha(sorted(glob.glob(os.path.join(csrc, "*.hip"))) + [os.path.join(csrc, "common.h"), os.path.join(csrc, "nc_shared.h"),
+                                                                   os.path.join(ROOT, "include", "mma_amd.h")])
 
 
 def loaded_kernel_sha():
