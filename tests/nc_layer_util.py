@@ -1,4 +1,5 @@
-"""What the GPU tests of the NC layer's newer kernels share (tests/test_nc_std_gpu.py, test_nc_bf16_gpu.py, test_nc_std_bf16_gpu.py):
+"""What the GPU tests of the NC layer's newer kernels share (tests/test_nc_std_gpu.py, test_nc_bf16_gpu.py, test_nc_std_bf16_gpu.py,
+test_nc_halo_gpu.py):
 the graphs, the plain torch statement of the `std` aggregator, the layer constructor and the std run.  Each graph is built once, here.
 
 Shapes are the smallest at which the kernels take another path: degrees around the group / wavefront item split and the 64-index
@@ -95,6 +96,33 @@ def hub_graph():
 def small_graph(N=150, seed=9):
     rng = np.random.default_rng(seed)
     return [sorted(rng.choice(N, size=rng.integers(0, 8), replace=False).tolist()) for _ in range(N)]
+
+
+def halo_graph():
+    """(add_all, S): the halo form of one shard - N = 150 targets (rows 0..149) over S = 300 source rows, rows 150..299 sources only.
+    Target 0 is a hub over own AND halo sources; targets 1..9 have the boundary in-degrees from halo sources alone; own source 10 and
+    halo source 290 have 100 out-edges each; halo sources 291..299 the boundary OUT-degrees; the other targets 2..6 more sources.  Some
+    own sources and halo source 291 have no out-edge at all."""
+    rng = np.random.default_rng(13)
+    N, S = 150, 300
+    edges = {(0, s) for s in range(60, 260)}
+    for k, d in enumerate(BOUNDARY_DEGREES):
+        for s in rng.choice(np.arange(150, 290), size=d, replace=False):
+            edges.add((1 + k, int(s)))
+    edges |= {(t, 10) for t in range(20, 120)} | {(t, 290) for t in range(30, 130)}
+    for k, d in enumerate(BOUNDARY_DEGREES):
+        for t in rng.choice(np.arange(20, 150), size=d, replace=False):
+            edges.add((int(t), 291 + k))
+    for t in range(10, N):
+        for s in rng.choice(np.arange(11, 290), size=rng.integers(2, 7), replace=False):
+            edges.add((t, int(s)))
+    return [sorted(s for (t, s) in edges if t == i) for i in range(N)], S
+
+
+def embed(add_all, S):
+    """The halo problem as an ordinary S-node graph: rows >= N take no in-edge (and, in the tests, a zero cotangent).  The oracles take
+    it unchanged with x of S rows; their m[:N], their full-S gx and their mask-weight gradients are the halo form's values."""
+    return add_all + [[]] * (S - len(add_all))
 
 
 BOUNDARY = boundary_graph()
