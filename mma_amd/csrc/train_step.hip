@@ -38,11 +38,14 @@ __global__ __launch_bounds__(kBlock) void logsoftmax_kernel(const float* x, int6
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < kMaxPerLane; ++i) if (lane + i * kWave < C) s += expf(v[i] - m);
-    const float lse = m + logf(wave_sum(s));
+    // (v - m) - log(sum), NOT v - (m + log(sum)): the second form rounds at the magnitude of the row maximum, which leaves
+    // every log-probability of the row - the ones near 0 too - with an absolute error of ulp(|m|); the backward's exp(logp) then
+    // carries it as a relative error (tests/test_train_step_kernels_gpu.py measured 1e-6 .. 3e-6 of gloss / n in dL/dlogits)
+    const float ls = logf(wave_sum(s));
 #pragma unroll
     for (int i = 0; i < kMaxPerLane; ++i) {
       const int c = lane + i * kWave;
-      if (c < C) logp[r * ldo + c] = v[i] - lse;
+      if (c < C) logp[r * ldo + c] = (v[i] - m) - ls;
     }
   }
 }
@@ -149,52 +152,76 @@ __global__ __launch_bounds__(kBlock) void adam_kernel(const AdamTensor* tab, int
 // mma.py:121 `x = F.relu(batch_norm(conv(...)))` inside the graphed Net step (train_step.GraphedNetStep): the batch is padded to a
 // static shape, so the statistics run over the first *n_valid rows (a DEVICE scalar: the captured graph replays on batches of any
 // size) while every row is normalised.  As torch ops the masked form is ~30 small launches per layer and direction.
-// One workgroup owns 4 columns: 64 row lanes x 4 columns, fixed summation order (a strided partial sum per row lane, then a tree); the
+// One workgroup owns 4 columns: 64 row lanes x 4 columns, fixed summation order (a strided partial sum per row lane, then a butterfly
+// over the 16 row lanes of a wavefront and the four wavefronts' sums in order); the
 // row loops fetch 8 rows per lane before they add (the batches of the graphed step are ~1 500 rows: with 16 columns per workgroup
 // and one load in flight per lane the two kernels took 48 / 77 us, a fifth of the whole Net step).
-constexpr int kBnCols = 4, kBnRows = kBlock / kBnCols, kBnAhead = 8;
+// The column sums (x, (x - mean)^2, g, g * xhat) are accumulated in DOUBLE, partial sums and reduction: a column of a few hundred fp32 terms
+// that cancel (the bias gradient of a layer whose cotangents change sign, x near 1000) otherwise carries the rounding of its largest
+// partial sum, several 1e-6 of the result where torch's reduction order happens to leave 1e-7.  The adds hide behind the row loads.
+constexpr int kBnCols = 4, kBnRows = kBlock / kBnCols, kBnAhead = 8, kBnWaves = kBlock / kWave, kBnSums = 3;
 
-__device__ __forceinline__ float bn_block_sum(float v, float (*red)[kBnCols], int r, int c) {
-  __syncthreads();
-  red[r][c] = v;
-  __syncthreads();
-  for (int o = kBnRows / 2; o > 0; o >>= 1) {
-    if (r < o) red[r][c] += red[r + o][c];
-    __syncthreads();
+// v[0..NV) summed over the row lanes of column c, in every thread: the lanes of a wavefront that share a column are kBnCols apart
+template <int NV>
+__device__ __forceinline__ void bn_block_sum(double (&v)[NV], double (*red)[kBnCols][kBnSums], int c) {
+#pragma unroll
+  for (int k = 0; k < NV; ++k)
+#pragma unroll
+    for (int o = kBnCols; o < kWave; o <<= 1) v[k] += __shfl_xor(v[k], o, kWave);
+  const int w = threadIdx.x / kWave;
+  __syncthreads();                                                     // the previous sums have been read
+  if ((threadIdx.x & (kWave - 1)) < kBnCols) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k) red[w][c][k] = v[k];
   }
-  return red[0][c];
+  __syncthreads();
+  static_assert(kBnWaves == 4 && NV <= kBnSums, "four wavefronts per workgroup");
+#pragma unroll
+  for (int k = 0; k < NV; ++k) v[k] = (red[0][c][k] + red[1][c][k]) + (red[2][c][k] + red[3][c][k]);
 }
 
 __global__ __launch_bounds__(kBlock) void masked_bn_relu_fwd_kernel(const float* x, int64_t ldx, const int64_t* n_valid, const float* gamma,
                                                                     const float* beta, float* y, int64_t ldy, float* mean_out, float* rstd_out,
                                                                     float* run_mean, float* run_var, int64_t* n_tracked, float momentum,
                                                                     float eps, int64_t N, int C, int relu) {
-  __shared__ float red[kBnRows][kBnCols];
+  __shared__ double red[kBnWaves][kBnCols][kBnSums];
   const int c = threadIdx.x % kBnCols, r = threadIdx.x / kBnCols;
   const int col = (int)blockIdx.x * kBnCols + c;
   const bool cv = col < C;
   const int64_t nv = min(max(*n_valid, (int64_t)1), N);
   const float cnt = (float)nv;
   const int xc = cv ? col : 0;                                         // lanes past C read column 0 and add nothing
-  float s = 0.f;
+  double s[1] = {0.}, q[1] = {0.}, s1 = 0., q1 = 0.;                 // even rows in flight in s / q, odd ones in s1 / q1: two add chains
   for (int64_t i = r; i < nv; i += kBnRows * kBnAhead) {
     float v[kBnAhead];
 #pragma unroll
     for (int u = 0; u < kBnAhead; ++u) { const int64_t j = i + u * kBnRows; v[u] = x[min(j, nv - 1) * ldx + xc]; }
 #pragma unroll
-    for (int u = 0; u < kBnAhead; ++u) s += (cv && i + u * kBnRows < nv) ? v[u] : 0.f;
+    for (int u = 0; u < kBnAhead; u += 2) {
+      s[0] += (cv && i + u * kBnRows < nv) ? (double)v[u] : 0.;
+      s1 += (cv && i + (u + 1) * kBnRows < nv) ? (double)v[u + 1] : 0.;
+    }
   }
-  const float mean = bn_block_sum(s, red, r, c) / cnt;
-  float q = 0.f;
+  s[0] += s1;
+  bn_block_sum(s, red, c);
+  const double mean_d = s[0] / (double)nv;
+  const float mean = (float)mean_d;
   for (int64_t i = r; i < nv; i += kBnRows * kBnAhead) {
     float v[kBnAhead];
 #pragma unroll
     for (int u = 0; u < kBnAhead; ++u) { const int64_t j = i + u * kBnRows; v[u] = x[min(j, nv - 1) * ldx + xc]; }
 #pragma unroll
-    for (int u = 0; u < kBnAhead; ++u) { const float d = (cv && i + u * kBnRows < nv) ? v[u] - mean : 0.f; q += d * d; }
+    for (int u = 0; u < kBnAhead; u += 2) {
+      const double d = (cv && i + u * kBnRows < nv) ? (double)v[u] - mean_d : 0.;
+      const double e = (cv && i + (u + 1) * kBnRows < nv) ? (double)v[u + 1] - mean_d : 0.;
+      q[0] += d * d; q1 += e * e;
+    }
   }
-  const float var = bn_block_sum(q, red, r, c) / cnt;                  // biased: what normalises (torch BatchNorm training mode)
-  const float rstd = rsqrtf(var + eps);
+  q[0] += q1;
+  bn_block_sum(q, red, c);
+  const double var_d = q[0] / (double)nv;                              // biased: what normalises (torch BatchNorm training mode)
+  const float var = (float)var_d;
+  const float rstd = (float)(1. / sqrt(var_d + (double)eps));            // one rounding: y of a padded row far from the mean carries rstd's
   if (cv) {
     const float g = gamma ? gamma[col] : 1.f, b = beta ? beta[col] : 0.f;
     for (int64_t i = r; i < N; i += kBnRows * kBnAhead) {
@@ -220,20 +247,23 @@ __global__ __launch_bounds__(kBlock) void masked_bn_relu_fwd_kernel(const float*
 }
 
 // g = gy * [y > 0] (ReLU);  gx = gamma rstd (g - sum(g)/n - xhat sum(g xhat)/n);  ggamma = sum(g xhat), gbeta = sum(g): sums over ALL rows -
-// the rows past n_valid belong to the dummy graph the loss never reads, their g is exactly 0
+// the rows past n_valid belong to the dummy graph the loss never reads, their g is exactly 0.
+// The saved mean is an fp32 number, off the batch mean by up to ulp(mean)/2: xhat built on it is off by that times rstd, in every row with
+// the same sign, and gx - whose largest term is xhat sum(g xhat)/n - with it (autograd's form is blind to it: its variance path meets
+// x - mean centred again).  So the first pass also sums x - mean over the valid rows: mean + that / n is the batch mean to double
+// precision, xhat is built on it and sum(g xhat) is put right by the same shift.
 __global__ __launch_bounds__(kBlock) void masked_bn_relu_bwd_kernel(const float* gy, int64_t ldg, const float* y, int64_t ldy, const float* x,
                                                                     int64_t ldx, const float* mean_in, const float* rstd_in, const float* gamma,
                                                                     const int64_t* n_valid, float* gx, int64_t ldgx, float* ggamma, float* gbeta,
                                                                     int64_t N, int C, int relu) {
-  __shared__ float red[kBnRows][kBnCols];
+  __shared__ double red[kBnWaves][kBnCols][kBnSums];
   const int c = threadIdx.x % kBnCols, r = threadIdx.x / kBnCols;
   const int col = (int)blockIdx.x * kBnCols + c;
   const bool cv = col < C;
   const int64_t nv = min(max(*n_valid, (int64_t)1), N);
-  const float cnt = (float)nv;
   const float mean = cv ? mean_in[col] : 0.f, rstd = cv ? rstd_in[col] : 0.f;
   const int xc = cv ? col : 0;
-  float sg = 0.f, sgx = 0.f;
+  double t[3] = {0., 0., 0.};                                         // sum(g), sum(g xhat), sum over the valid rows of x - mean
   for (int64_t i = r; i < N; i += kBnRows * kBnAhead) {
     float vy[kBnAhead], vg[kBnAhead], vx[kBnAhead];
 #pragma unroll
@@ -245,12 +275,19 @@ __global__ __launch_bounds__(kBlock) void masked_bn_relu_bwd_kernel(const float*
     for (int u = 0; u < kBnAhead; ++u) {
       if (cv && i + u * kBnRows < N) {
         const float g = (relu && !(vy[u] > 0.f)) ? 0.f : vg[u];
-        sg += g; sgx += g * ((vx[u] - mean) * rstd);
+        const double d = (double)vx[u] - (double)mean;
+        t[0] += (double)g; t[1] += (double)g * (d * (double)rstd);
+        if (i + u * kBnRows < nv) t[2] += d;
       }
     }
   }
-  const float tg = bn_block_sum(sg, red, r, c);
-  const float tgx = bn_block_sum(sgx, red, r, c);
+  bn_block_sum(t, red, c);
+  const double tg_d = t[0];
+  const double shift = t[2] / (double)nv;                              // batch mean - saved mean
+  const double mean_d = (double)mean + shift;
+  const double tgx_d = t[1] - shift * (double)rstd * tg_d;             // sum(g xhat) on the batch mean
+  const float tg = (float)tg_d, tgx = (float)tgx_d;
+  const float mg = (float)(tg_d / (double)nv), mgx = (float)(tgx_d / (double)nv);      // sum(g) / n, sum(g xhat) / n
   if (cv) {
     const float k = (gamma ? gamma[col] : 1.f) * rstd;
     for (int64_t i = r; i < N; i += kBnRows * kBnAhead) {
@@ -264,9 +301,9 @@ __global__ __launch_bounds__(kBlock) void masked_bn_relu_bwd_kernel(const float*
       for (int u = 0; u < kBnAhead; ++u) {
         const int64_t j = i + u * kBnRows;
         const float g = (relu && !(vy[u] > 0.f)) ? 0.f : vg[u];
-        const float xh = (vx[u] - mean) * rstd;
+        const float xh = (float)(((double)vx[u] - mean_d) * (double)rstd);
         // the statistics depend on the first nv rows only: a padded row's x reaches nothing but its own y
-        if (j < N) gx[j * ldgx + col] = j < nv ? k * (g - tg / cnt - xh * (tgx / cnt)) : k * g;
+        if (j < N) gx[j * ldgx + col] = j < nv ? k * (g - mg - xh * mgx) : k * g;
       }
     }
     if (r == 0) { if (ggamma) ggamma[col] = tgx; if (gbeta) gbeta[col] = tg; }
@@ -295,12 +332,12 @@ extern "C" int mma_logsoftmax_nll_fwd(const float* x, int64_t ldx, const int64_t
               (long long)N, (long long)n_idx, C);
   if (N == 0) return 0;
   MMA_REQUIRE(x && logp, "NULL argument");
+  MMA_REQUIRE(!loss || (n_idx > 0 && idx && labels), "the loss needs a non-empty idx and the labels");      // before ANY launch
   hipStream_t st = static_cast<hipStream_t>(stream);
   int64_t blocks = (N + 3) / 4;
   if (blocks > kMaxGrid) blocks = kMaxGrid;
   hipLaunchKernelGGL(logsoftmax_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, x, ldx, logp, ldo, N, C);
   if (loss) {
-    MMA_REQUIRE(n_idx > 0 && idx && labels, "the loss needs a non-empty idx and the labels");
     hipLaunchKernelGGL(nll_mean_kernel, dim3(1), dim3(kBlock), 0, st, logp, ldo, idx, labels, n_idx, loss, N, C);
   }
   return check_launch("logsoftmax_nll_fwd");

@@ -75,20 +75,22 @@ def test_words_are_a_function_of_the_global_edge_id_and_the_seed():
 
 
 @pytest.mark.gpu
-def test_seed_advance_is_splitmix64():
-    """mma_seed_advance (the one captured launch that redraws a layer's dropout seeds per replay) against its restatement."""
+@pytest.mark.parametrize("n", [5, 64, 65, 200])
+def test_seed_advance_is_splitmix64(n):
+    """mma_seed_advance (the one captured launch that redraws a layer's dropout seeds per replay) against its restatement: part of a
+    64-thread block, one full block, one block and a thread, several blocks."""
     import torch
     from mma_amd import functional as Fn
     from oracle.dropout_rng import splitmix64
-    ds = Fn.DeviceSeeds(5, torch.device("cuda:0"))
-    states = [int(v) & ((1 << 64) - 1) for v in ds.buf[5:].tolist()]
+    ds = Fn.DeviceSeeds(n, torch.device("cuda:0"))
+    states = [int(v) & ((1 << 64) - 1) for v in ds.buf[n:].tolist()]
     for _ in range(3):
         got = [int(v) & ((1 << 64) - 1) for v in ds.advance().tolist()]
         nxt = [splitmix64(s) for s in states]
         states = [a for a, _ in nxt]
         assert got == [b for _, b in nxt]
-        assert [int(v) & ((1 << 64) - 1) for v in ds.buf[5:].tolist()] == states
-    assert len(set(got)) == 5
+        assert [int(v) & ((1 << 64) - 1) for v in ds.buf[n:].tolist()] == states
+    assert len(set(got)) == n
 
 
 def test_hash_dropout_applies_any_probability_to_16_bits():

@@ -175,6 +175,120 @@ def test_mmaconv_with_wide_aggregate_blocks_takes_the_unfactored_post_nn():
     assert (gx.cpu().double() - g64).abs().max().item() <= 5e-5 * g64.abs().max().item()
 
 
+def test_factor_scalers_switch_both_sides_against_the_oracle(monkeypatch):
+    """MMA_FACTOR_SCALERS (mma_conv.FACTOR_SCALERS): on, the degree scalers are row factors inside the post-NN (Fn.tower_post on the K
+    unscaled aggregates); off, K3 scales and the post-NN is the strided-batched GEMM over the (N, T, S*K*Fw) aggregate
+    (dense.tower_linear).  One small layer, both sides: output, dL/dx and every parameter gradient against the float64 oracle, and the call
+    sites each side must take."""
+    import mma_amd
+    from mma_amd import dense, functional as Fn, mma_conv as MC
+    from oracle import gr_oracle as G
+    from tools.synth import molecule_batch
+    from test_gr_gpu import conv_params, to64
+    rng = np.random.default_rng(5)
+    torch.manual_seed(1)
+    T, F, aggs, scalers = 2, 8, ["sum", "mean", "min", "max"], ["identity", "amplification", "attenuation"]
+    conv = mma_amd.MMAConv(F, 12, aggs, scalers, torch.tensor([0, 10, 30, 50, 10]), edge_dim=None, towers=T).to(DEV)
+    assert conv.F_out <= 16 and dense.tower_post_fits(len(aggs) * conv.fused_width(), len(scalers)), "the on side must be inside K13's limits"
+    monkeypatch.setattr(MC, "ACCUMULATE_UNREGISTERED", False)     # torch.autograd.grad below asks for the mask Linears' gradients
+    conv.drop_override = Fn.DropoutSpec(0.0)
+    ei, N = molecule_batch(rng, 40)
+    x = rng.standard_normal((N, F)).astype(np.float32)
+    cot = torch.from_numpy(rng.standard_normal((N, conv.out_channels)))
+    lins = [seq[0].active_linear() for seq in conv.pre_nns[aggs[-1]]]
+    params = {"pre_w": [l.weight for l in lins], "pre_b": [l.bias for l in lins], "post_w": [s[0].weight for s in conv.post_nns],
+              "post_b": [s[0].bias for s in conv.post_nns], "lin_w": [conv.lin.weight], "lin_b": [conv.lin.bias]}
+    names = [(k, i) for k, v in params.items() for i in range(len(v))]
+    # float64 oracle
+    prm64 = to64(conv_params(conv))
+    leaves64 = []
+    for k, i in names:
+        if isinstance(prm64[k], list):
+            prm64[k][i].requires_grad_(True)
+            leaves64.append(prm64[k][i])
+        else:
+            leaves64.append(prm64[k].requires_grad_(True))
+    x64 = torch.from_numpy(x).double().requires_grad_(True)
+    want = G.conv_forward(x64, torch.from_numpy(ei), None, prm64, conv.aggregators, conv.scalers, conv.avg_deg, T, False, None, 0.0)
+    g64 = torch.autograd.grad((want * cot).sum(), [x64] + leaves64)
+
+    seen = []
+    real_post, real_linear = Fn.tower_post, dense.tower_linear
+    monkeypatch.setattr(Fn, "tower_post", lambda agg, *a, **k: (seen.append(("tower_post", tuple(agg.shape))), real_post(agg, *a, **k))[1])
+    monkeypatch.setattr(dense, "tower_linear", lambda out, *a, **k: (seen.append(("tower_linear", tuple(out.shape))), real_linear(out, *a, **k))[1])
+    KFw, S = len(aggs) * conv.fused_width(), len(scalers)
+    for on in (True, False):
+        monkeypatch.setattr(MC, "FACTOR_SCALERS", on)
+        del seen[:]
+        xg = torch.from_numpy(x).to(DEV).requires_grad_(True)
+        got = conv(xg, torch.from_numpy(ei).to(DEV))
+        gg = torch.autograd.grad((got * cot.float().to(DEV)).sum(), [xg] + [params[k][i] for k, i in names])
+        assert seen == ([("tower_post", (N, T, KFw))] if on else [("tower_linear", (N, T, S * KFw))]), (on, seen)
+        err = (got.cpu().double() - want.detach()).abs().max().item()
+        assert err <= 2e-5 * want.abs().max().item(), (on, "forward", err)
+        for (k, i), a, b in zip([("x", 0)] + names, gg, g64):
+            err = (a.cpu().double() - b).abs().max().item()
+            assert err <= 5e-5 * b.abs().max().item(), (on, k, i, err, b.abs().max().item())
+
+
+ADDEND_SHAPES = [(4500, 75, 75), (4097, 3, 1), (4200, 129, 33)]
+
+
+@pytest.mark.parametrize("N,K,O", ADDEND_SHAPES)
+def test_skinny_linear_addend_epilogue_against_float64(N, K, O):
+    """K16's `addend` epilogue (mma_skinny_linear_fwd(..., addend, ldadd, ...), reached through dense.linear(x, W, b, addend=)):
+    y = x W^T + b + addend with the addend a column slice of a wider buffer (ldadd > O), under test_skinny_linear_against_float64's bar;
+    the gradients of x, W, b against float64, the addend's gradient is the cotangent itself."""
+    from mma_amd import dense
+    g = torch.Generator().manual_seed(N + K + O + 1)
+    x, W, b = torch.randn(N, K, generator=g), torch.randn(O, K, generator=g) / np.sqrt(K), torch.randn(O, generator=g)
+    wide = torch.randn(N, O + 5, generator=g)
+    cot = torch.randn(N, O, generator=g)
+    x64, w64, b64 = x.double().requires_grad_(True), W.double().requires_grad_(True), b.double().requires_grad_(True)
+    a64 = wide[:, 2:2 + O].double()
+    y64 = torch.nn.functional.linear(x64, w64, b64) + a64
+    gr = torch.autograd.grad((y64 * cot.double()).sum(), [x64, w64, b64])
+    xd, wd, bd = x.to(DEV).requires_grad_(True), W.to(DEV).requires_grad_(True), b.to(DEV).requires_grad_(True)
+    wide_d = wide.to(DEV).requires_grad_(True)
+    add = wide_d[:, 2:2 + O]
+    assert dense._skinny_ok(xd, wd) and add.stride(0) == O + 5, "this shape must take the K16 path, with a pitched addend"
+    y = dense.linear(xd, wd, bd, addend=add)
+    cot_d = cot.to(DEV)
+    gx, gw, gb, ga = torch.autograd.grad((y * cot_d).sum(), [xd, wd, bd, add])
+    mag = x.double().abs() @ W.double().abs().t() + b.double().abs() + a64.abs()
+    assert ((y.cpu().double() - y64.detach()).abs() <= 3e-7 * mag + 1e-9).all(), (y.cpu().double() - y64.detach()).abs().max().item()
+    for got, ref, what in zip((gx, gw, gb), gr, ("gx", "gW", "gb")):
+        err = (got.cpu().double() - ref).abs().max().item()
+        assert err <= 2e-5 * ref.abs().max().item() + 1e-7, (what, err)
+    assert torch.equal(ga, cot_d), "d y / d addend is the identity: the cotangent itself, bit for bit"
+    gwide, = torch.autograd.grad((dense.linear(xd, wd, bd, addend=wide_d[:, 2:2 + O]) * cot_d).sum(), [wide_d])
+    assert torch.equal(gwide[:, 2:2 + O], cot_d) and not gwide[:, :2].any() and not gwide[:, 2 + O:].any()
+
+
+def test_linear_with_an_addend_on_the_library_path():
+    """The other branch of `_Linear.forward`: a shape `_skinny_ok` refuses (too few rows) adds the addend after the library GEMM."""
+    from mma_amd import dense
+    g = torch.Generator().manual_seed(9)
+    N, K, O = 300, 75, 75
+    x, W, b = torch.randn(N, K, generator=g), torch.randn(O, K, generator=g) / np.sqrt(K), torch.randn(O, generator=g)
+    wide, cot = torch.randn(N, O + 5, generator=g), torch.randn(N, O, generator=g)
+    x64, w64, b64 = x.double().requires_grad_(True), W.double().requires_grad_(True), b.double().requires_grad_(True)
+    a64 = wide[:, 2:2 + O].double()
+    y64 = torch.nn.functional.linear(x64, w64, b64) + a64
+    gr = torch.autograd.grad((y64 * cot.double()).sum(), [x64, w64, b64])
+    xd, wd, bd = x.to(DEV).requires_grad_(True), W.to(DEV).requires_grad_(True), b.to(DEV).requires_grad_(True)
+    add = wide.to(DEV)[:, 2:2 + O].requires_grad_(True)
+    assert not dense._skinny_ok(xd, wd)
+    y = dense.linear(xd, wd, bd, addend=add)
+    gx, gw, gb, ga = torch.autograd.grad((y * cot.to(DEV)).sum(), [xd, wd, bd, add])
+    mag = x.double().abs() @ W.double().abs().t() + b.double().abs() + a64.abs()
+    assert ((y.cpu().double() - y64.detach()).abs() <= 3e-7 * mag + 1e-9).all(), (y.cpu().double() - y64.detach()).abs().max().item()
+    for got, ref, what in zip((gx, gw, gb), gr, ("gx", "gW", "gb")):
+        err = (got.cpu().double() - ref).abs().max().item()
+        assert err <= 2e-5 * ref.abs().max().item() + 1e-7, (what, err)
+    assert torch.equal(ga, cot.to(DEV))
+
+
 def test_batched_tn_product_against_float64():
     from mma_amd import dense
     g = torch.Generator().manual_seed(1)
