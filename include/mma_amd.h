@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MMA_ABI_VERSION 40
+#define MMA_ABI_VERSION 41
 #define MMA_MAX_K 8          /* masks fused per launch; more are issued as several launches */
 
 /* combine kinds of the node-classification aggregators (layers.py:201-728) */
@@ -65,8 +65,11 @@ const char* mma_build_stamp(void);
  *     T[i, k*H+h]   = sum_j drop * act_k'(z) * x_j[h]          (so grad_P = gs * T needs no edge pass)
  *     sel[i, k*H+h] = 0: x_i selected  1: s selected  2: tie (0.5/0.5, torch.max/min backward)  3: NaN
  * and/or (ABI 27) the packed code row the shared-gradient backward gathers per edge:
- *     crow[i] = [ 1/max(d_i,1), 0, 0, 0 | for every max/min/softmax/softmin mask, in mask order: ceil(H/4) words of bytes
- *                 = 2 * dm/ds of the element (0: x_i selected, 1: tie, 2: s selected, 255: NaN gradient) ]
+ *     crow[i] = [ 1/max(d_i,1), 0, 0, 0 | for every max/min/softmax/softmin mask, in mask order: a slot of ceil(H/16) words that
+ *                 holds 2 bits per element (ABI 41; element h in byte h/4 at bits 2(h%4)) = 2 * dm/ds of the element
+ *                 (0: x_i selected, 1: tie, 2: s selected, 3: NaN gradient) | unused up to the pitch ]
+ *     The layout depends on (H, kinds) alone.  mma_nc_crow_floats still returns the row length of the byte-per-element rows of
+ *     ABI 27..40, 4 + n_sel * ceil(H/4) rounded up to 4; the slots fill the front of it and the rest is neither written nor read.
  *     (round 2 had K2a write a [g | 1/d | codes] row per target: 0.8 GB per step at C4 that K1 now leaves in place of `sel`).
  */
 int mma_nc_fused_fwd(

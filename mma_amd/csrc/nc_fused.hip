@@ -36,9 +36,9 @@ struct NcFwdParamsT {
   float* msum; int64_t ldms;         // (N,H) sum over the K masks, may be NULL
   float* T; uint8_t* sel; int64_t ldt;
   // shared-gradient backward (round 3): K1 itself leaves the packed code row K2b gathers per edge,
-  // crow[i] = [ 1/d_i, 0, 0, 0 | one byte per element for every max/min/softmax-type mask = 2 * dm/ds (0, 1, 2; 255: NaN) ]
+  // crow[i] = [ 1/d_i, 0, 0, 0 | 2 bits per element for every max/min/softmax-type mask = 2 * dm/ds (0, 1, 2; 3: NaN) ]: see crow_slot
   float* crow; int64_t ldc; uint32_t sel_slots;      // 4 bits per mask: its code slot in the row, 0xF = none (sum / mean)
-  int H, HQ, K_total, k_base, lpr_log;
+  int H, HQ, K_total, k_base, lpr_log;               // HQ: words per code slot (crow_slot_words)
   uint32_t kinds, acts;              // 4 bits / 1 bit per mask, indexed by absolute k
   DropParams drop;
   // one-launch form (nc_fwd_small_kernel): the hub list and the ticket counter of the chunk partials
@@ -48,12 +48,44 @@ using NcFwdParams = NcFwdParamsT<float>;
 
 __device__ __forceinline__ int kind_of(uint32_t kinds, int k) { return (kinds >> (4 * k)) & 0xF; }
 __device__ __forceinline__ uint32_t sel_slot_of(uint32_t slots, int k) { return (slots >> (4 * k)) & 0xFu; }
-// the VEC code bytes of mask k at column c of a packed code row (NcFwdParams::crow); `dflt` for a mask without a slot (sum / mean)
+// The packed code row (NcFwdParams::crow).  The code slots follow the 16-byte header back to back, HQ = ceil(H/16) words each; a
+// slot holds 2 bits per element, element c in byte c/4 at bits 2(c%4).  The layout is a function of (H, kinds) alone: a VEC = 4
+// lane owns exactly one byte, four VEC = 1 lanes share one, and either form reads what the other wrote.
+__host__ __device__ __forceinline__ int crow_slot_words(int H) { return (H + 15) / 16; }
+__device__ __forceinline__ const uint8_t* crow_slot(const float* crow_row, uint32_t sslot, int HQ, int c) {
+  return reinterpret_cast<const uint8_t*>(crow_row + 4 + (size_t)sslot * HQ) + (c >> 2);
+}
+// the VEC 2-bit codes of one slot at column c, code i in bits 2i
+template <int VEC>
+__device__ __forceinline__ uint32_t crow_slot_codes(const float* crow_row, uint32_t sslot, int HQ, int c) {
+  const uint32_t b = *crow_slot(crow_row, sslot, HQ, c);
+  return VEC == 4 ? b : (b >> (2 * (c & 3))) & 3u;
+}
+// ... of mask k; `dflt` for a mask without a slot (sum / mean)
 template <int VEC>
 __device__ __forceinline__ uint32_t crow_codes(const float* crow_row, uint32_t sel_slots, int k, int HQ, int c, uint32_t dflt) {
   const uint32_t sslot = sel_slot_of(sel_slots, k);
-  return sslot != 0xFu ? ldb<VEC>(reinterpret_cast<const uint8_t*>(crow_row + 4 + (size_t)sslot * HQ) + c) : dflt;
+  return sslot != 0xFu ? crow_slot_codes<VEC>(crow_row, sslot, HQ, c) : dflt;
 }
+// The writer.  VEC = 4: the lane's four codes are its byte.  VEC = 1: the (up to four) lanes of a row that share a byte meet in a
+// quad exchange and the lane of element c % 4 == 0 stores it - never a read-modify-write of memory.  All lanes of such a quad must
+// make the call; `on` is false for those that hold no element (c >= H).  `lpr` is the lanes per row of the caller (a row of 1 or 2
+// lanes shares its quad with other rows, whose codes must stay out).
+template <int VEC>
+__device__ __forceinline__ void crow_store(float* crow_row, uint32_t sslot, int HQ, int c, uint32_t tf, bool on, int lpr) {
+  uint8_t* dst = const_cast<uint8_t*>(crow_slot(crow_row, sslot, HQ, c));
+  if (VEC == 4) {
+    if (on) *dst = (uint8_t)tf;
+  } else {
+    uint32_t f = on ? tf << (2 * (c & 3)) : 0u;
+    if (lpr >= 2) f |= __shfl_xor(f, 1, kWave);
+    if (lpr >= 4) f |= __shfl_xor(f, 2, kWave);
+    if (on && (c & 3) == 0) *dst = (uint8_t)f;
+  }
+}
+
+// threads per hub row of nc_fwd_finalize_kernel: one per VEC columns; VEC = 1 rounds up to whole quads (see crow_store)
+__host__ __device__ __forceinline__ int nc_finalize_per_row(int H, int vec) { return vec == 4 ? (H + 3) / 4 : (H + 3) & ~3; }
 
 // combine + selection code for one element (layers.py:221,326-329,452,562,676-682,716-720)
 __device__ __forceinline__ float nc_combine(int kind, float xi, float s, float deg, uint32_t& code) {
@@ -75,9 +107,11 @@ __device__ __forceinline__ float nc_combine(int kind, float xi, float s, float d
   }
 }
 
+// `on`: the lane holds an element (always, for VEC = 4).  A VEC = 1 lane past the end of the row (c >= H) comes along for the quad
+// exchange of crow_store (`lpr`: see there) with the operands of column 0 and stores nothing.
 template <int VEC, bool SAVE, class PP>
 __device__ __forceinline__ Vec<VEC> nc_fwd_write(const PP& p, int node, int k_abs, int c, const Vec<VEC>& xi,
-                                                 const Vec<VEC>& s, const Vec<VEC>& t, float deg) {
+                                                 const Vec<VEC>& s, const Vec<VEC>& t, float deg, bool on, int lpr) {
   Vec<VEC> mo;
   uint32_t codes = 0;
   const int kind = kind_of(p.kinds, k_abs);
@@ -87,20 +121,23 @@ __device__ __forceinline__ Vec<VEC> nc_fwd_write(const PP& p, int node, int k_ab
     mo.v[i] = nc_combine(kind, xi.v[i], s.v[i], deg, code);
     codes |= code << (8 * i);
   }
-  if (p.m) stv<VEC>(p.m + (size_t)k_abs * p.m_kstride + (size_t)node * p.H + c, mo);
+  if (p.m && on) stv<VEC>(p.m + (size_t)k_abs * p.m_kstride + (size_t)node * p.H + c, mo);
   if (SAVE) {
     const size_t o = (size_t)node * p.ldt + (size_t)k_abs * p.H + c;
-    stv_nt<VEC>(p.T + o, t);
-    if (p.sel) stb_nt<VEC>(p.sel + o, codes);
+    if (on) {
+      stv_nt<VEC>(p.T + o, t);
+      if (p.sel) stb_nt<VEC>(p.sel + o, codes);
+    }
     if (p.crow && sel_slot_of(p.sel_slots, k_abs) != 0xFu) {
-      // code -> 2 * dm/ds: 1 (s selected) -> 2, 2 (tie) -> 1, 0 (x_i selected) -> 0, 3 (NaN gradient) -> 255
+      // code -> 2 * dm/ds: 1 (s selected) -> 2, 2 (tie) -> 1, 0 (x_i selected) -> 0, 3 (NaN gradient) -> 3
       uint32_t tf = 0;
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
         const uint32_t code = (codes >> (8 * i)) & 0xFFu;
-        tf |= (code == 1u ? 2u : (code == 2u ? 1u : (code == 3u ? 255u : 0u))) << (8 * i);
+        tf |= (code == 1u ? 2u : (code == 2u ? 1u : code)) << (2 * i);
       }
-      stb<VEC>(reinterpret_cast<uint8_t*>(p.crow + (size_t)node * p.ldc + 4 + (size_t)sel_slot_of(p.sel_slots, k_abs) * p.HQ) + c, tf);   // re-read per edge by K2b: plain store
+      // re-read per edge by K2b: plain store
+      crow_store<VEC>(p.crow + (size_t)node * p.ldc, sel_slot_of(p.sel_slots, k_abs), p.HQ, c, tf, on, lpr);
     }
   }
   return mo;
@@ -257,19 +294,23 @@ __device__ __forceinline__ void nc_fwd_body(const NcFwdParamsT<TT>& p, const int
         }
     }
 
-    if (sub == 0 && fvalid && ivalid) {
+    // VEC = 1: the lanes of a row past its end (c >= H) take the direct branch with the others - they share code bytes with them
+    // (crow_store) - and store nothing
+    const bool writer = sub == 0 && fvalid && ivalid;
+    if (VEC == 1 ? (sub == 0 && ivalid) : writer) {
+      const bool on = VEC == 1 ? writer : true;
       if (slot < 0) {
         const float deg = (float)max(p.rowptr[node + 1] - p.rowptr[node], 1);
         Vec<VEC> ms = vzero<VEC>();
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-          const Vec<VEC> mo = nc_fwd_write<VEC, SAVE>(p, node, p.k_base + k, c, xi, acc[k], tac[k], deg);
+          const Vec<VEC> mo = nc_fwd_write<VEC, SAVE>(p, node, p.k_base + k, c, xi, acc[k], tac[k], deg, on, lpr);
 #pragma unroll
           for (int i = 0; i < VEC; ++i) ms.v[i] += mo.v[i];
         }
-        if (p.msum) nc_msum_store<VEC>(p, node, c, ms, p.k_base > 0);
+        if (p.msum && on) nc_msum_store<VEC>(p, node, c, ms, p.k_base > 0);
         if (SAVE && p.crow && c == 0 && p.k_base == 0) p.crow[(size_t)node * p.ldc] = 1.f / deg;
-      } else {
+      } else if (on) {
         float* ps = p.partial + (size_t)slot * p.pstride;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -302,10 +343,14 @@ __global__ __launch_bounds__(kBlock, (K <= 4 ? MMA_MIN_WAVES : 1)) void nc_fwd_k
 // hub nodes: sum the chunk partials in slot order, then the same epilogue
 template <int VEC, bool SAVE, class PP>
 __device__ __forceinline__ void nc_fwd_finalize_body(const PP& p, const int4* hubs, int64_t n_hubs, const int64_t first, const int64_t step) {
-  const int per_row = (p.H + VEC - 1) / VEC;
+  // VEC = 1: a row takes a multiple of four threads (nc_finalize_per_row), so that the four elements of a code byte sit in one
+  // aligned quad (crow_store); the threads past the end of the row work on column 0 and store nothing
+  const int per_row = nc_finalize_per_row(p.H, VEC);
   const int64_t total = n_hubs * per_row;
   for (int64_t idx = first; idx < total; idx += step) {
-    const int c = (int)(idx % per_row) * VEC;
+    const int c0 = (int)(idx % per_row) * VEC;
+    const bool on = c0 < p.H;
+    const int c = on ? c0 : 0;
     const int4 hub = hubs[idx / per_row];
     const int node = hub.x;
     const Vec<VEC> xi = ldv<VEC>(p.x + (size_t)node * p.ldx + c);
@@ -336,12 +381,12 @@ __device__ __forceinline__ void nc_fwd_finalize_body(const PP& p, const int4* hu
           }
         }
       }
-      const Vec<VEC> mo = nc_fwd_write<VEC, SAVE>(p, node, k, c, xi, s, t, deg);
+      const Vec<VEC> mo = nc_fwd_write<VEC, SAVE>(p, node, k, c0, xi, s, t, deg, on, 4);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) ms.v[i] += mo.v[i];
     }
-    if (p.msum) nc_msum_store<VEC>(p, node, c, ms, false);
-    if (SAVE && p.crow && c == 0) p.crow[(size_t)node * p.ldc] = 1.f / deg;
+    if (p.msum && on) nc_msum_store<VEC>(p, node, c, ms, false);
+    if (SAVE && p.crow && c0 == 0) p.crow[(size_t)node * p.ldc] = 1.f / deg;
   }
 }
 template <int VEC, bool SAVE, class TT = float>
@@ -380,7 +425,7 @@ struct NcBwdNodeParams {
   uint32_t* rowmax;        // optional: max |gP| per node (bits of a non-negative float), merged with K2b's max |gQ| by atomicMax
 };
 
-// dm/ds and dm/dx_i of one element from the packed byte tf = 2 * dm/ds of a max/min/softmax-type mask (255: NaN gradient), or
+// dm/ds and dm/dx_i of one element from the 2-bit code tf = 2 * dm/ds of a max/min/softmax-type mask (3: NaN gradient), or
 // from the kind alone for sum / mean
 __device__ __forceinline__ void combine_grad_tf(int kind, uint32_t tf, float inv_deg, float& fs, float& fx) {
   switch (kind) {
@@ -388,7 +433,7 @@ __device__ __forceinline__ void combine_grad_tf(int kind, uint32_t tf, float inv
     case MMA_KIND_MEAN: fs = inv_deg; fx = inv_deg; break;
     case MMA_KIND_MAX:
     case MMA_KIND_MIN: fs = 0.5f * (float)tf; fx = 1.f - fs; break;
-    default: fs = tf == 255u ? __builtin_nanf("") : 1.f; fx = 0.f; break;
+    default: fs = tf == 3u ? __builtin_nanf("") : 1.f; fx = 0.f; break;
   }
 }
 
@@ -432,8 +477,8 @@ __global__ __launch_bounds__(kBlock) void nc_bwd_node_kernel(const NcBwdNodePara
         Vec<VEC> gsv, gpv;
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
-          uint32_t tf = (codes >> (8 * i)) & 0xFFu;
-          if (!p.crow) tf = tf == 1u ? 2u : (tf == 2u ? 1u : (tf == 3u ? 255u : 0u));     // sel code -> 2 * dm/ds
+          uint32_t tf = p.crow ? (codes >> (2 * i)) & 3u : (codes >> (8 * i)) & 0xFFu;     // code row: 2 bits; sel: a byte per element
+          if (!p.crow) tf = tf == 1u ? 2u : (tf == 2u ? 1u : tf);     // sel code -> 2 * dm/ds
           float fs, fx;  // d m / d s, d m / d x_i
           combine_grad_tf(kind, tf, inv_deg, fs, fx);
           gsv.v[i] = g.v[i] * fs;
@@ -507,7 +552,7 @@ __device__ __forceinline__ Vec<VEC> nc_bwd_epilogue(const PP& p, int node, int c
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
         float fs, fx;
-        combine_grad_tf(kind, (ck[k] >> (8 * i)) & 0xFFu, inv_deg, fs, fx);
+        combine_grad_tf(kind, (ck[k] >> (2 * i)) & 3u, inv_deg, fs, fx);
         gpv.v[i] = (g.v[i] * fs) * tk[k].v[i];
         gxd.v[i] = fmaf(g.v[i], fx, gxd.v[i]);
         mx = fmaxf(mx, fabsf(gpv.v[i]));
@@ -608,7 +653,7 @@ __device__ __forceinline__ void nc_bwd_body(const NcBwdParamsT<TT>& p, const int
             for (int k = 0; k < K; ++k) {
               // sum/mean never look at the code: a constant "s selected" (2 = twice the factor 1.0) keeps the arithmetic
               // below branch-free
-              codes[u][k] = crow_codes<VEC>(crow, p.sel_slots, p.k_base + k, p.HQ, cc, 0x02020202u);
+              codes[u][k] = crow_codes<VEC>(crow, p.sel_slots, p.k_base + k, p.HQ, cc, 0xAAu);
             }
           }
           const TT* prow = p.P + row_off(ii, p.ldp) + cc;
@@ -632,7 +677,7 @@ __device__ __forceinline__ void nc_bwd_body(const NcBwdParamsT<TT>& p, const int
           for (int k = 0; k < K; ++k) {
             const bool raw = (p.acts >> (p.k_base + k)) & 1u;
             const int kind = SHARED ? kind_of(p.kinds, p.k_base + k) : 0;
-            const float kscale = 0.5f * (kind == MMA_KIND_MEAN ? idg[u] : 1.f);   // the code byte holds TWICE dm/ds
+            const float kscale = 0.5f * (kind == MMA_KIND_MEAN ? idg[u] : 1.f);   // the code is TWICE dm/ds
             float f[VEC];
             if (DM == MMA_DROP_HASH) {
               drop_unpack<VEC>(dp, drop_mask_word(hw, k == 0 ? p.k_base : 1, mult[k]), cc, f);     // k > 0: never the base word (compile time)
@@ -652,9 +697,9 @@ __device__ __forceinline__ void nc_bwd_body(const NcBwdParamsT<TT>& p, const int
               else { a = sigmoid_fast(z); da = a - a * a; }
               float gsv;
               if (SHARED) {
-                const uint32_t tf = (codes[u][k] >> (8 * i)) & 0xFFu;      // v_cvt_f32_ubyte<i>
+                const uint32_t tf = (codes[u][k] >> (2 * i)) & 3u;         // v_bfe_u32 + v_cvt_f32_ubyte0
                 float cf = (float)tf;
-                if (kind >= MMA_KIND_SOFTMAX && tf == 255u) cf = __builtin_nanf("");   // exp overflow in the forward combine
+                if (kind >= MMA_KIND_SOFTMAX && tf == 3u) cf = __builtin_nanf("");   // exp overflow in the forward combine
                 gsv = gv[u][0].v[i] * (cf * kscale);
               } else {
                 gsv = gv[u][k].v[i];
@@ -809,11 +854,11 @@ __device__ __forceinline__ void nc_bwd_finalize_body(const PP& p, const int4* hu
         for (int kk = 0; kk < p.K_total; ++kk) {
           // written out (not crow_codes): the helper moves instructions in nc_bwd_finalize_kernel<1>
           const uint32_t sslot = sel_slot_of(p.sel_slots, kk);
-          const uint32_t ck = sslot != 0xFu ? ldb<VEC>(reinterpret_cast<const uint8_t*>(crow + 4 + (size_t)sslot * p.HQ) + c) : 0u;
+          const uint32_t ck = sslot != 0xFu ? crow_slot_codes<VEC>(crow, sslot, p.HQ, c) : 0u;
 #pragma unroll
           for (int i = 0; i < VEC; ++i) {
             float fs, fx;
-            combine_grad_tf(kind_of(p.kinds, kk), (ck >> (8 * i)) & 0xFFu, inv_deg, fs, fx);
+            combine_grad_tf(kind_of(p.kinds, kk), (ck >> (2 * i)) & 3u, inv_deg, fs, fx);
             g0.v[i] = fmaf(g.v[i], fx, g0.v[i]);
           }
         }
@@ -863,7 +908,8 @@ static int pack_codes(const uint8_t* kind_host, const uint8_t* act_host, int K, 
 }
 
 // sel-kinds (max/min/softmax/softmin) get consecutive code slots in the packed code row (4 bits per mask, 0xF = none); returns the
-// row length in floats: [ 1/d_i, 0, 0, 0 | n_sel * ceil(H/4) words of codes ], rounded up to a multiple of 4
+// row length in floats: 4 + n_sel * ceil(H/4), rounded up to a multiple of 4.  That is the length of the byte-per-element rows of
+// ABI <= 40 and stays the pitch callers allocate; the 2-bit slots (crow_slot_words) fill the front of it, the rest is never touched.
 static int64_t fill_sel_slots(const uint8_t* kind_host, int K, int H, uint32_t* slots) {
   int n = 0;
   *slots = 0xFFFFFFFFu;
@@ -1015,7 +1061,7 @@ static int nc_fused_fwd(
   p.partial = partial; p.pstride = 2LL * K * H;
   p.m = m; p.m_kstride = N * (int64_t)H; p.msum = m_sum; p.ldms = ldms; p.T = T; p.sel = sel; p.ldt = ldt;
   p.crow = crow; p.ldc = ldc;
-  p.H = H; p.HQ = (H + 3) / 4; p.K_total = K; p.lpr_log = g.lpr_log; p.kinds = kinds; p.acts = acts;
+  p.H = H; p.HQ = crow_slot_words(H); p.K_total = K; p.lpr_log = g.lpr_log; p.kinds = kinds; p.acts = acts;
   hipStream_t st = static_cast<hipStream_t>(stream);
   n_wave_items = nc_wave_items(kWave >> g.lpr_log, n_items, n_wave_items);
   {
@@ -1032,7 +1078,7 @@ static int nc_fused_fwd(
   });
   if (int rc = check_launch("nc_fwd_kernel")) return rc;
   if (n_hubs > 0) {
-    const int per_row = (H + g.vec - 1) / g.vec;
+    const int per_row = nc_finalize_per_row(H, g.vec);
     const dim3 fg = elementwise_grid(n_hubs * per_row);
     const int4* hb = reinterpret_cast<const int4*>(hubs);
     with_flag(g.vec == 4, [&](auto v4) { with_flag(save, [&](auto sv) {
@@ -1102,7 +1148,7 @@ extern "C" int mma_nc_bwd_node(
   if (int rc = pack_codes(kind_host, nullptr, K, &kinds, &acts)) return rc;
   NcBwdNodeParams p{g, g_kstride, ldgr, sel, T, ldt, rowptr, gs, ldgs, gP, ldgp, gxs, ldgx, N, H, K, kinds};
   p.rowmax = reinterpret_cast<uint32_t*>(row_max);
-  p.crow = crow; p.ldc = ldc; p.HQ = (H + 3) / 4;
+  p.crow = crow; p.ldc = ldc; p.HQ = crow_slot_words(H);
   const int64_t crow_len = fill_sel_slots(kind_host, K, H, &p.sel_slots);
   MMA_REQUIRE(!crow || (ldc >= crow_len && ldc % 4 == 0 && aligned16(crow)),
               "crow needs a 16-byte aligned pitch >= %lld floats (mma_nc_crow_floats)", (long long)crow_len);
@@ -1169,7 +1215,7 @@ static int nc_fused_bwd(
   p.t_col = t_col; p.t_eid = t_eid; p.items = reinterpret_cast<const int4*>(items); p.n_items = n_items;
   p.partial = partial; p.pstride = (int64_t)(K + 1) * H; p.gQ = gQ; p.ldgq = ldgq; p.gx = gx; p.ldgxo = ldgxo;
   p.rowmax = reinterpret_cast<uint32_t*>(row_max);
-  p.H = H; p.HQ = (H + 3) / 4; p.K_total = K; p.lpr_log = geo.lpr_log; p.acts = acts;
+  p.H = H; p.HQ = crow_slot_words(H); p.K_total = K; p.lpr_log = geo.lpr_log; p.acts = acts;
   hipStream_t st = static_cast<hipStream_t>(stream);
   n_wave_items = nc_wave_items(kWave >> geo.lpr_log, n_items, n_wave_items);
   {

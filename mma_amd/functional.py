@@ -127,7 +127,8 @@ def nc_fwd_launch(x_src, P, Q, graph, kinds, acts, drop, reduce_k, save, shared=
     crow = None
     if save and shared:
         ldc = crow_floats(H, kinds)
-        # zeros: the padding of a row (and, for H % 4 != 0, the tail of a code word) is never written by the kernel
+        # the kernel writes 1/d and the 2-bit codes at the front of a row (ABI 41) and nothing else: floats 1..3, the bytes that round a
+        # code slot up to a word and everything behind the slots stay as allocated (never read either; zeros where H % 4 != 0, as before)
         crow = (torch.zeros if H % 4 else torch.empty)((N, ldc), device=dev, dtype=torch.float32)
     partial = torch.empty((graph.n_slots, 2 * K * H), device=dev, dtype=torch.float32) if graph.n_slots else None
     if drop.keep is not None:
