@@ -161,7 +161,13 @@ __global__ __launch_bounds__(kBlock) void tower_post_pre_kernel(const PostParams
 // y[n, t*O + o] = sum_q pre_q sum_kf agg[n, t*KF + kf] * Wa[t][kf][q*16 + o]
 // PLAIN: a plain skinny Linear, y[n, r] = bias[r] + sum_kf x[n, kf] * Wa[kf][r] for r < O <= S*16 - every 16-row tile is 16 more
 // outputs instead of one more scaler (the 75 -> 75 Linear layers around the fused kernels: x-part of the post-NN, `lin`)
-template <int S, bool PLAIN, bool VEC4>
+// BLOCKED: the products of every 32-column tile round are summed in an accumulator of their own that joins the running sum once per
+// round.  The shapes whose split weights do not fit the LDS (KFp * S > 1706: S >= 4 near the LDS limit) take this kernel by default, and
+// one fp32 chain over their 384 .. 512 products sat at 3.1e-7 sum|x||w| of float64 - over the 3e-7 both forward forms keep
+// (tests/test_tower_post_edges_gpu.py: K16 at (4160, 384, 80)); chains of 32 and KFp/32 additions of whole rounds stay well under it.
+// Those shapes hold one workgroup per CU (>= 145 KB of LDS), so the S x 16 registers more cost no occupancy.  BLOCKED = false is the
+// kernel as it was, bit for bit: MMA_POST_EXACT=1, MMA_SKINNY_X3=0 and K16's addend epilogue at the shapes the pieces would fit.
+template <int S, bool PLAIN, bool VEC4, bool BLOCKED = false>
 __global__ __launch_bounds__(kBlock) void tower_post_fwd_kernel(const PostParams p, const float* __restrict__ agg, const float* __restrict__ pre_tab,
                                                                 const float* __restrict__ Wa, float* __restrict__ y) {
   extern __shared__ __attribute__((aligned(16))) float post_smem[];
@@ -192,6 +198,11 @@ __global__ __launch_bounds__(kBlock) void tower_post_fwd_kernel(const PostParams
     post_tile_put(tile, lane, nxt);
     post_wave_sync();
     if (kf0 + kPostTile < p.KFp) post_tile_fetch<VEC4>(p, agg, n0, t, kf0 + kPostTile, lane, nxt);   // in flight behind the MFMAs
+    post_f32x4 blk[4][S];                                        // BLOCKED: this round's sum (unused otherwise)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int q = 0; q < S; ++q) blk[nt][q] = post_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < kPostTile / 4; ++ks) {
       const int kf = kf0 + 4 * ks + kq;
@@ -205,8 +216,15 @@ __global__ __launch_bounds__(kBlock) void tower_post_fwd_kernel(const PostParams
 #pragma unroll
         for (int q = 0; q < S; ++q) {
           if (kPostAbl & 16) { asm volatile("" : "+v"(acc[nt][q]) : "v"(a[q]), "v"(b[nt])); }
+          else if (BLOCKED) blk[nt][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q], b[nt], blk[nt][q], 0, 0, 0);
           else acc[nt][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q], b[nt], acc[nt][q], 0, 0, 0);
         }
+    }
+    if (BLOCKED) {
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int q = 0; q < S; ++q) acc[nt][q] += blk[nt][q];
     }
     post_wave_sync();
   }
@@ -821,6 +839,10 @@ using namespace mma;
     case 4: hipLaunchKernelGGL((KERNEL<4, PLAIN, V4>), grid, dim3(kBlock), LDS, st, p, __VA_ARGS__); break;            \
     default: hipLaunchKernelGGL((KERNEL<5, PLAIN, V4>), grid, dim3(kBlock), LDS, st, p, __VA_ARGS__); break;           \
   }
+// the BLOCKED form of the fp32 forward: only shapes whose split weights do not fit the LDS take it, and those have S >= 4
+#define MMA_POST_LAUNCH_BLOCKED(PLAIN, V4, LDS, ...)                                                                                        \
+  if (S == 4) hipLaunchKernelGGL((tower_post_fwd_kernel<4, PLAIN, V4, true>), grid, dim3(kBlock), LDS, st, p, __VA_ARGS__);              \
+  else hipLaunchKernelGGL((tower_post_fwd_kernel<5, PLAIN, V4, true>), grid, dim3(kBlock), LDS, st, p, __VA_ARGS__);
 #define MMA_POST_LAUNCH2(KERNEL, PLAIN, LDS, ...)                                                                      \
   switch (S) {                                                                                                         \
     case 1: hipLaunchKernelGGL((KERNEL<1, PLAIN>), grid, dim3(kBlock), LDS, st, p, __VA_ARGS__); break;                \
@@ -915,12 +937,17 @@ extern "C" int mma_tower_post_fwd(const float* agg, int64_t lda, const float* pr
   p.tiles_per_wave = post_tiles_per_wave(N, T);
   if (const char* e = getenv("MMA_POST_TPW")) { if (atoi(e) > 0) p.tiles_per_wave = atoi(e); }      // plan sweep (tools/post_micro.py)
   const dim3 grid = post_grid(p, T);
-  if (const unsigned lx = post_x3_lds_bytes(p.KFp, S); lx <= 160 * 1024 && !post_exact()) {
+  const unsigned lx = post_x3_lds_bytes(p.KFp, S);
+  if (lx <= 160 * 1024 && !post_exact()) {
     if (p.vec4) { MMA_POST_LAUNCH2(tower_post_fwd_x3_kernel, true, lx, agg, pre, Wa, y) } else { MMA_POST_LAUNCH2(tower_post_fwd_x3_kernel, false, lx, agg, pre, Wa, y) }
     return check_launch("tower_post_fwd_x3_kernel");
   }
   const unsigned lds = post_lds_bytes(p.KFp, S, false);
   MMA_REQUIRE(lds <= 160 * 1024, "the tower's weights (%u bytes with the tiles) do not fit the LDS", lds);
+  if (lx > 160 * 1024 && S >= 4) {      // no bf16-piece form for this shape: the fp32 forward is its default, summed round by round
+    if (p.vec4) { MMA_POST_LAUNCH_BLOCKED(false, true, lds, agg, pre, Wa, y) } else { MMA_POST_LAUNCH_BLOCKED(false, false, lds, agg, pre, Wa, y) }
+    return check_launch("tower_post_fwd_kernel (blocked)");
+  }
   if (p.vec4) { MMA_POST_LAUNCH3(tower_post_fwd_kernel, false, true, lds, agg, pre, Wa, y) } else { MMA_POST_LAUNCH3(tower_post_fwd_kernel, false, false, lds, agg, pre, Wa, y) }
   return check_launch("tower_post_fwd_kernel");
 }
@@ -1042,7 +1069,8 @@ extern "C" int mma_skinny_linear_fwd(const float* x, int64_t ldx, const float* W
   const float* pre = nullptr;
   // [r5] on three bf16 pieces per operand (tower_post_fwd_x3_kernel<.., PLAIN>) where the split weights fit the LDS; MMA_POST_EXACT=1 or an
   // addend: the exact-fp32 kernel
-  if (const unsigned lx = post_x3_lds_bytes(p.KFp, S); lx <= 160 * 1024 && !post_exact() && !addend) {
+  const unsigned lx = post_x3_lds_bytes(p.KFp, S);
+  if (lx <= 160 * 1024 && !post_exact() && !addend) {
     const char* e = getenv("MMA_SKINNY_X3");                    // read per call (A/B): 0 = the fp32 kernel
     if (!(e && e[0] == '0')) {
 #define MMA_SK(SS, V4) hipLaunchKernelGGL((tower_post_fwd_x3_kernel<SS, V4, true>), grid, dim3(kBlock), lx, st, p, x, pre, Wa, y)
@@ -1059,6 +1087,10 @@ extern "C" int mma_skinny_linear_fwd(const float* x, int64_t ldx, const float* W
   }
   const unsigned lds = post_lds_bytes(p.KFp, S, false);
   MMA_REQUIRE(lds <= 160 * 1024, "the weights (%u bytes with the tiles) do not fit the LDS", lds);
+  if (lx > 160 * 1024 && S >= 4) {      // no bf16-piece form for this shape: the fp32 forward is its default, summed round by round
+    if (p.vec4) { MMA_POST_LAUNCH_BLOCKED(true, true, lds, x, pre, Wa, y) } else { MMA_POST_LAUNCH_BLOCKED(true, false, lds, x, pre, Wa, y) }
+    return check_launch("tower_post_fwd_kernel (plain, blocked)");
+  }
   if (p.vec4) { MMA_POST_LAUNCH3(tower_post_fwd_kernel, true, true, lds, x, pre, Wa, y) } else { MMA_POST_LAUNCH3(tower_post_fwd_kernel, true, false, lds, x, pre, Wa, y) }
   return check_launch("tower_post_fwd_kernel (plain)");
 }

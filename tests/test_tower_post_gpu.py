@@ -6,20 +6,11 @@ import numpy as np
 import pytest
 import torch
 
+from tower_post_ref import pre64 as _pre           # the running scaler products in float64: one copy, shared with the edge tests
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SC = ["identity", "amplification", "attenuation", "linear", "inverse_linear"]
-
-
-def _pre(deg, scalers, avg_log, avg_lin):
-    d = deg.clamp(min=1).double()
-    lg = torch.log(d + 1)
-    f = {"identity": torch.ones_like(d), "amplification": lg / avg_log, "attenuation": avg_log / lg, "linear": d / avg_lin, "inverse_linear": avg_lin / d}
-    run, out = torch.ones_like(d), []
-    for s in scalers:
-        run = run * f[s]
-        out.append(run)
-    return torch.stack(out, 1)                                    # (N, S)
 
 
 @pytest.mark.parametrize("N,T,KF,O,scalers", [(1000, 5, 152, 15, SC[:1] + SC[1:2] + SC[3:4]), (77, 1, 4, 1, SC[:1]), (4097, 3, 36, 16, SC),
