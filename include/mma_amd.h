@@ -376,7 +376,9 @@ int mma_gemm_bf16x3_tn_batched(const float* X, int64_t ldx, int64_t xb, const fl
  * are per ROW of both operands, balanced between them (x_i 2^a and g_i 2^-a leave x_i g_i unchanged) so that ONE un-scaling serves
  * the whole product; they are derived on the device from the row maxima: x_row_max / g_row_max (M,) >= max |.| of every row of X /
  * G (0 marks an all-zero row), either may be NULL (then one extra pass over that operand forms them; the backward kernels
- * produce G's: mma_nc_bwd_node / mma_nc_fused_bwd).  |error| <= 2^-22 sum|x||g| + M 2^-39 max_i(max|x_i| max|g_i|).  If some row's
+ * produce G's: mma_nc_bwd_node / mma_nc_fused_bwd).  |error| <= 2^-22 sum|x||g| + M 2^-39 max_i(max|x_i| max|g_i|) where an element
+ * sums many comparable rows; ONE product alone can be off by 3 * 2^-22 of itself (each operand's lo piece rounds at 2^-11 of a value that
+ * is up to 2^-11 of the element, and lo lo is dropped): an element that a single row makes up (M = 33) was met at 5.3e-7.  If some row's
  * products lie more than 2^40 below the largest row's, or a row maximum is inf / NaN / subnormal, the six-product kernel
  * (mma_gemm_bf16x3_tn) does the call instead - decided on the device, no synchronisation.  Shapes as mma_gemm_bf16x3_tn, M < 2^30,
  * and KA up to 256 (round 4: eight waves share one staged tile of G, which is then read once for hidden width 256 - same bits as
