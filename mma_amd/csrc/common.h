@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <type_traits>
 #include "../../include/mma_amd.h"
 
 namespace mma {
@@ -240,5 +241,9 @@ __device__ __forceinline__ uint32_t bf16_rne(float f) {
 }
 
 __host__ inline int ilog2_ceil(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
+
+// host side, run-time value -> template argument: f receives it as a std::integral_constant (a generic lambda reads decltype(v)::value)
+template <int V> using ic = std::integral_constant<int, V>;
+template <class F> static void with_flag(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 
 }  // namespace mma

@@ -10,7 +10,6 @@
 // lowest edge position exactly like torch_scatter's sequential CPU kernel, and the sub-row butterfly keeps that
 // order by comparing (value, edge id) lexicographically.
 #include "common.h"
-#include <type_traits>
 #include <hipcub/hipcub.hpp>
 #include <limits.h>
 
@@ -40,7 +39,9 @@ struct GrParams {
   int nb; uint32_t qd, qd_magic, f_magic;            // flat kernels: nodes per workgroup, lanes (VEC columns each) per row, 2^32/d magics
   // block kernels: float4s per node / per tower / per aggregate block of `out`, with their magics; LDS byte offsets
   uint32_t tskf4, m_tskf4, skf4, m_skf4, f4, m_f4, m_k;
-  uint32_t lds_agg, lds_arg, lds_bytes; int n_coef;
+  uint32_t lds_agg, lds_arg, lds_bytes;
+  int n_coef;                   // set by gr_block_mode, never read on the device (the backward block kernel counts its planes from NEEDS):
+                                // it stays because a removed field would move the kernarg offset of every field behind it
   const uint8_t* zidx;          // categorical edge features: Z is a small table and its row for an edge is zidx[position or edge id]
   const int32_t* long_nodes;                         // optional [count, node ids...] of the segments above kGroupMaxDeg (mma_build_csr)
   int long_cap;                                      // ids the list can hold (mma_gr_long_nodes_len(E) - 1): a count beyond it is not believed
@@ -269,6 +270,11 @@ __device__ __forceinline__ void gr_factor_table(const GrParams& p, float (*tab)[
   }
   __syncthreads();
 }
+// the row of one degree out of a staged table (gr_factor_table, or fac / pre of the block kernels' blk_stage)
+__device__ __forceinline__ void gr_factor_row(const float (*tab)[8], int deg, float (&fac)[8]) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q) fac[q] = tab[deg][q];
+}
 
 // VEC = 4 (F % 4 == 0 and 16-byte aligned rows everywhere): a lane owns 4 consecutive columns of one tower and moves one
 // dwordx4 per row, also for the (N,T,S*K*F) output.  Otherwise VEC = 1: lanes own consecutive columns, so all accesses
@@ -315,17 +321,20 @@ __device__ __forceinline__ void gr_node_fwd(const GrParams& p, const DropParams&
   gr_fwd_store<VEC>(p, l, node, s.b, s.e - s.b, a, fac);
 }
 
-// second pass behind the flat / block kernels when mma_build_csr listed the long segments: one wave per listed node
-template <int VEC>
-__global__ __launch_bounds__(kBlock) void gr_fwd_list_kernel(const GrParams p) {
+// ---- the list pass: second pass behind the flat / block kernels when mma_build_csr listed the long segments, one wave per listed
+// node.  gr_list_count and gr_for_listed_nodes are ALL that reads the list: the number of ids to walk, and the walk.  (Two functions:
+// the kernels resolve the dropout seed and the lane geometry between them, where they always did.)
+__device__ __forceinline__ int gr_list_count(const GrParams& p) {
   const int raw_count = p.long_nodes[0];
   const int count = min(raw_count, p.long_cap);          // never walk past the list, whatever the count word holds -
   // - but SAY so (round-4 ADVICE: a clobbered count or id would otherwise drop long segments silently): the word behind the list is an
   // error flag the host reads outside capture (functional.DeviceCSR.check)
   if ((raw_count < 0 || raw_count > p.long_cap) && blockIdx.x == 0 && threadIdx.x == 0) const_cast<int32_t*>(p.long_nodes)[1 + p.long_cap] = 1;
-  if (count <= 0) return;
-  const DropParams dp = drop_resolve(p.drop);
-  const GrLane l = gr_lane(p, VEC);
+  return count;
+}
+// f(node) for the listed nodes of this wavefront (wave w of the grid takes ids w, w + waves, ...)
+template <class F>
+__device__ __forceinline__ void gr_for_listed_nodes(const GrParams& p, int count, F&& f) {
   const int stride = (int)gridDim.x * (kBlock / kWave);
   for (int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6))); i < count; i += stride) {
     const int n = __builtin_amdgcn_readfirstlane(p.long_nodes[1 + i]);
@@ -333,11 +342,22 @@ __global__ __launch_bounds__(kBlock) void gr_fwd_list_kernel(const GrParams p) {
       if ((threadIdx.x & (kWave - 1)) == 0) const_cast<int32_t*>(p.long_nodes)[1 + p.long_cap] = 2;
       continue;
     }
+    f(n);
+  }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(kBlock) void gr_fwd_list_kernel(const GrParams p) {
+  const int count = gr_list_count(p);
+  if (count <= 0) return;
+  const DropParams dp = drop_resolve(p.drop);
+  const GrLane l = gr_lane(p, VEC);
+  gr_for_listed_nodes(p, count, [&](int n) {
     const Seg s = seg_load(p, n);
     const SegIdx i0 = idx_load(p, s.b, s.e, l.lane);
     const Vec<VEC> u0 = l.fused ? ldv<VEC>(p.U + (size_t)n * p.lduv + l.cc) : vzero<VEC>();
     gr_node_fwd<VEC>(p, dp, l, n, s, i0, u0);
-  }
+  });
 }
 
 template <int VEC>
@@ -388,6 +408,9 @@ __device__ __forceinline__ GrLane flat_lane(const GrParams& p, int q, bool fused
   return l;
 }
 
+// The node-block / item walk (slots, flat_node_block, item decode, long-segment skip) is written out in both flat kernels, token for
+// token - change them together: as a shared function, with the body passed in or as decode helpers, neither kernel kept its instructions
+// (they sit at the SGPR limit; DESIGN.md, "Shared parts of gr_fused.hip").
 template <int VEC>
 __global__ __launch_bounds__(kBlock) void gr_fwd_flat_kernel(const GrParams p) {
   __shared__ float fac_tab[kGroupMaxDeg + 1][8];
@@ -429,8 +452,7 @@ __global__ __launch_bounds__(kBlock) void gr_fwd_flat_kernel(const GrParams p) {
         a.take(p, gr_message<VEC>(p, dp, fused, u, jj, (uint32_t)ee, (uint32_t)(b + t), l.c), t);
       }
       float fac[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) fac[q] = fac_tab[deg][q];
+      gr_factor_row(fac_tab, deg, fac);
       gr_fwd_store<VEC>(p, l, node, b, deg, a, fac);
     }
   }
@@ -488,6 +510,16 @@ __device__ __forceinline__ void gr_bwd_coef(const GrParams& p, const GrLane& l, 
   }
 }
 
+// a lane's VEC columns of a row merged into the row's maximum (the bit pattern of a non-negative float in a zeroed word): the generic
+// and flat kernels merge per lane in global memory (the block kernel reduces in LDS first)
+template <int VEC>
+__device__ __forceinline__ void rmax_merge(uint32_t* slot, const Vec<VEC>& v) {
+  float m = 0.f;
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) m = fmaxf(m, fabsf(v.v[i]));
+  if (m > 0.f) atomicMax(slot, __float_as_uint(m));
+}
+
 // gradient of the edge at position pos (offset off in its segment, original id e, source j); written to gmsg[pos or e]
 template <int VEC>
 __device__ __forceinline__ Vec<VEC> gr_bwd_edge(const GrParams& p, const DropParams& dp, const GrLane& l, const GrCoef<VEC>& k_,
@@ -508,12 +540,7 @@ __device__ __forceinline__ Vec<VEC> gr_bwd_edge(const GrParams& p, const DropPar
     g.v[i] = gi * fd[i];
   }
   stv<VEC>(p.gmsg + (size_t)(p.by_pos ? pos : e) * p.ldg + l.cc, g);
-  if (p.gmsg_rmax) {                                          // wave-uniform; the generic kernels merge per lane (the block kernel reduces in LDS first)
-    float m = 0.f;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) m = fmaxf(m, fabsf(g.v[i]));
-    if (m > 0.f) atomicMax(p.gmsg_rmax + (p.by_pos ? pos : e), __float_as_uint(m));
-  }
+  if (p.gmsg_rmax) rmax_merge<VEC>(p.gmsg_rmax + (p.by_pos ? pos : e), g);     // wave-uniform
   return g;
 }
 
@@ -552,36 +579,21 @@ __device__ __forceinline__ void gr_node_bwd(const GrParams& p, const DropParams&
     }
     if (l.sub == 0 && l.valid) {
       stv<VEC>(p.gU + (size_t)node * p.ldgu + l.c, su);
-      if (p.gu_rmax) {
-        float m = 0.f;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) m = fmaxf(m, fabsf(su.v[i]));
-        if (m > 0.f) atomicMax(p.gu_rmax + node, __float_as_uint(m));
-      }
+      if (p.gu_rmax) rmax_merge<VEC>(p.gu_rmax + node, su);
     }
   }
 }
 
 template <int VEC>
 __global__ __launch_bounds__(kBlock) void gr_bwd_list_kernel(const GrParams p) {
-  const int raw_count = p.long_nodes[0];
-  const int count = min(raw_count, p.long_cap);          // never walk past the list, whatever the count word holds -
-  // - but SAY so (round-4 ADVICE: a clobbered count or id would otherwise drop long segments silently): the word behind the list is an
-  // error flag the host reads outside capture (functional.DeviceCSR.check)
-  if ((raw_count < 0 || raw_count > p.long_cap) && blockIdx.x == 0 && threadIdx.x == 0) const_cast<int32_t*>(p.long_nodes)[1 + p.long_cap] = 1;
+  const int count = gr_list_count(p);
   if (count <= 0) return;
   const DropParams dp = drop_resolve(p.drop);
   const GrLane l = gr_lane(p, VEC);
-  const int stride = (int)gridDim.x * (kBlock / kWave);
-  for (int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6))); i < count; i += stride) {
-    const int n = __builtin_amdgcn_readfirstlane(p.long_nodes[1 + i]);
-    if ((unsigned)n >= (unsigned)p.N) {
-      if ((threadIdx.x & (kWave - 1)) == 0) const_cast<int32_t*>(p.long_nodes)[1 + p.long_cap] = 2;
-      continue;
-    }
+  gr_for_listed_nodes(p, count, [&](int n) {
     const Seg s = seg_load(p, n);
     gr_node_bwd<VEC>(p, dp, l, n, s, idx_load(p, s.b, s.e, l.lane));
-  }
+  });
 }
 
 template <int VEC>
@@ -627,8 +639,7 @@ __global__ __launch_bounds__(kBlock) void gr_bwd_flat_kernel(const GrParams p) {
       Vec<VEC> su = vzero<VEC>();                             // dL/dU[node]: this lane walks the whole segment, so it is a local sum
       if (deg > 0) {
         float fac[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) fac[q] = fac_tab[deg][q];
+        gr_factor_row(fac_tab, deg, fac);
         GrCoef<VEC> k_;
         gr_bwd_coef<VEC>(p, l, node, b, deg, (float)deg, fac, k_);
         const Vec<VEC> u = (fused && k_.need_h) ? ldv<VEC>(p.U + (size_t)node * p.lduv + l.c) : vzero<VEC>();
@@ -642,12 +653,7 @@ __global__ __launch_bounds__(kBlock) void gr_bwd_flat_kernel(const GrParams p) {
       }
       if (p.gU) {
         stv<VEC>(p.gU + (size_t)node * p.ldgu + l.c, su);
-        if (p.gu_rmax) {
-          float m = 0.f;
-#pragma unroll
-          for (int cidx = 0; cidx < VEC; ++cidx) m = fmaxf(m, fabsf(su.v[cidx]));
-          if (m > 0.f) atomicMax(p.gu_rmax + node, __float_as_uint(m));
-        }
+        if (p.gu_rmax) rmax_merge<VEC>(p.gu_rmax + node, su);
       }
     }
   }
@@ -670,7 +676,6 @@ __global__ __launch_bounds__(kBlock) void gr_bwd_flat_kernel(const GrParams p) {
 constexpr int kBlkCap = 256;         // edge positions of a block staged in LDS (src, perm); blocks with more read them from memory
 constexpr int kBlkMaxKS = 8;         // backward: gradient blocks (K*S) loaded per item in one batch
 enum { NEED_SUM = 1, NEED_MIN = 2, NEED_MAX = 4 };
-
 
 struct BlkLds {
   float (*fac)[8]; float (*pre)[8]; int* rowptr; int* src; int* perm; uint8_t* zt; float* agg; uint8_t* arg;
@@ -769,46 +774,56 @@ __device__ __forceinline__ Vec<4> blk_combine(const GrParams& p, const DropParam
   return v;
 }
 
+// item `it` of a block that starts at node n0: node n0 + dn, columns [c, c + 4), segment [b, b + deg) from the staged row pointers.
+// For blk_fwd_items and the edge phase of the backward.  The backward's coefficient phase and the forward's arg write-out keep their
+// own decode: through this function their kernels no longer compile to the same instructions ("Shared parts of gr_fused.hip").
+struct BlkItem { int dn, c, node, b, deg; };
+__device__ __forceinline__ BlkItem blk_item(const GrParams& p, const BlkLds& L, int n0, int it) {
+  BlkItem x;
+  x.dn = (int)udiv((uint32_t)it, p.qd_magic);
+  x.c = (it - x.dn * (int)p.qd) * 4;
+  x.node = n0 + x.dn;
+  x.b = L.rowptr[x.dn]; x.deg = L.rowptr[x.dn + 1] - x.b;
+  return x;
+}
+
 template <bool FUSED, bool HASZ, bool DROP, int NEEDS, bool STAGED>
 __device__ __forceinline__ void blk_fwd_items(const GrParams& p, const DropParams& dp, const BlkLds& L, int n0, int n_here, int p0) {
   const int items = n_here * (int)p.qd;
   for (int it = threadIdx.x; it < items; it += kBlock) {
-    const int dn = (int)udiv((uint32_t)it, p.qd_magic);
-    const int c = (it - dn * (int)p.qd) * 4;
-    const int node = n0 + dn;
-    const int b = L.rowptr[dn], deg = L.rowptr[dn + 1] - b;
-    if (deg > kGroupMaxDeg) continue;                         // a long segment: left to the wave-per-node pass
+    const BlkItem x = blk_item(p, L, n0, it);
+    if (x.deg > kGroupMaxDeg) continue;                       // a long segment: left to the wave-per-node pass
     // ---- the item's loads, all issued before the first use: U row + three edge slots (slot i = edge min(i, deg-1); an
     // empty segment re-reads the block's first edge and drops it - the block has one: a block without edges never gets here, the
     // kernel's p1 == p0 branch writes its zeros, so position p0 < p1 <= E is a staged word of this workgroup or an edge of the CSR)
     int j[3], e[3], pos[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      pos[i] = deg > 0 ? b + min(i, deg - 1) : p0;
+      pos[i] = x.deg > 0 ? x.b + min(i, x.deg - 1) : p0;
       if (STAGED) { j[i] = L.src[pos[i] - p0]; e[i] = L.perm[pos[i] - p0]; }
       else { j[i] = p.src[pos[i]]; e[i] = p.perm[pos[i]]; }
     }
-    const Vec<4> u = FUSED ? ldv<4>(p.U + (size_t)node * p.lduv + c) : vzero<4>();
+    const Vec<4> u = FUSED ? ldv<4>(p.U + (size_t)x.node * p.lduv + x.c) : vzero<4>();
     Vec<4> v[3], z[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      v[i] = FUSED ? ldv<4>(p.V + (size_t)j[i] * p.lduv + c) : ldv<4>(p.inputs + (size_t)e[i] * p.ldi + c);
+      v[i] = FUSED ? ldv<4>(p.V + (size_t)j[i] * p.lduv + x.c) : ldv<4>(p.inputs + (size_t)e[i] * p.ldi + x.c);
       const size_t zr = (STAGED && p.zidx) ? (size_t)L.zt[pos[i] - p0] : gr_zrow(p, pos[i], e[i]);
-      z[i] = (FUSED && HASZ) ? ldv<4>(p.Z + zr * p.ldz + c) : vzero<4>();
+      z[i] = (FUSED && HASZ) ? ldv<4>(p.Z + zr * p.ldz + x.c) : vzero<4>();
     }
     BlkAcc<NEEDS> a;
     a.init();
 #pragma unroll
-    for (int i = 0; i < 3; ++i) a.take(blk_combine<FUSED, HASZ, DROP>(p, dp, u, v[i], z[i], (uint32_t)e[i], c), i, i < deg);
-    for (int t = 3; t < deg; ++t) {                           // rare on molecule batches (degree-4 atoms)
-      const int pt = b + t;
+    for (int i = 0; i < 3; ++i) a.take(blk_combine<FUSED, HASZ, DROP>(p, dp, u, v[i], z[i], (uint32_t)e[i], x.c), i, i < x.deg);
+    for (int t = 3; t < x.deg; ++t) {                           // rare on molecule batches (degree-4 atoms)
+      const int pt = x.b + t;
       const int jj = STAGED ? L.src[pt - p0] : p.src[pt], ee = STAGED ? L.perm[pt - p0] : p.perm[pt];
-      const Vec<4> vv = FUSED ? ldv<4>(p.V + (size_t)jj * p.lduv + c) : ldv<4>(p.inputs + (size_t)ee * p.ldi + c);
+      const Vec<4> vv = FUSED ? ldv<4>(p.V + (size_t)jj * p.lduv + x.c) : ldv<4>(p.inputs + (size_t)ee * p.ldi + x.c);
       const size_t zrr = (STAGED && p.zidx) ? (size_t)L.zt[pt - p0] : gr_zrow(p, pt, ee);
-      const Vec<4> zz = (FUSED && HASZ) ? ldv<4>(p.Z + zrr * p.ldz + c) : vzero<4>();
-      a.take(blk_combine<FUSED, HASZ, DROP>(p, dp, u, vv, zz, (uint32_t)ee, c), t, true);
+      const Vec<4> zz = (FUSED && HASZ) ? ldv<4>(p.Z + zrr * p.ldz + x.c) : vzero<4>();
+      a.take(blk_combine<FUSED, HASZ, DROP>(p, dp, u, vv, zz, (uint32_t)ee, x.c), t, true);
     }
-    const float fdeg = (float)max(deg, 1);                    // degree(...).clamp_(1), mma_conv.py:178-179
+    const float fdeg = (float)max(x.deg, 1);                    // degree(...).clamp_(1), mma_conv.py:178-179
     for (int k = 0; k < p.K; ++k) {
       const int code = (int)((p.aggr_pack >> (4 * k)) & 15u);
       Vec<4> r;
@@ -816,23 +831,23 @@ __device__ __forceinline__ void blk_fwd_items(const GrParams& p, const DropParam
       for (int i = 0; i < 4; ++i) {
         float val = 0.f;
         if (NEEDS & NEED_SUM) val = code == GR_SUM ? a.sum[i] : (code == GR_MEAN ? a.sum[i] / fdeg : val);   // scatter mean: sum / clamp(count, 1)
-        if (NEEDS & NEED_MIN) val = code == GR_MIN ? (deg ? a.mn[i] : 0.f) : val;                            // empty target -> 0 (torch_scatter)
-        if (NEEDS & NEED_MAX) val = code == GR_MAX ? (deg ? a.mx[i] : 0.f) : val;
+        if (NEEDS & NEED_MIN) val = code == GR_MIN ? (x.deg ? a.mn[i] : 0.f) : val;                            // empty target -> 0 (torch_scatter)
+        if (NEEDS & NEED_MAX) val = code == GR_MAX ? (x.deg ? a.mx[i] : 0.f) : val;
         r.v[i] = val;
       }
-      stv<4>(L.agg + ((size_t)dn * p.K + k) * p.D + c, r);
+      stv<4>(L.agg + ((size_t)x.dn * p.K + k) * p.D + x.c, r);
     }
     if ((NEEDS & NEED_MIN) && p.amin8) {
       uint32_t w = 0;
 #pragma unroll
       for (int i = 0; i < 4; ++i) w |= ((uint32_t)a.an[i] & 0xFFu) << (8 * i);
-      *reinterpret_cast<uint32_t*>(L.arg + (size_t)dn * p.D + c) = w;
+      *reinterpret_cast<uint32_t*>(L.arg + (size_t)x.dn * p.D + x.c) = w;
     }
     if ((NEEDS & NEED_MAX) && p.amax8) {
       uint32_t w = 0;
 #pragma unroll
       for (int i = 0; i < 4; ++i) w |= ((uint32_t)a.ax[i] & 0xFFu) << (8 * i);
-      *reinterpret_cast<uint32_t*>(L.arg + (size_t)(p.nb + dn) * p.D + c) = w;
+      *reinterpret_cast<uint32_t*>(L.arg + (size_t)(p.nb + x.dn) * p.D + x.c) = w;
     }
   }
 }
@@ -969,12 +984,10 @@ __global__ __launch_bounds__(kBlock) void gr_bwd_block_kernel(const GrParams p) 
   auto phase_b = [&](auto fast_c) {
   constexpr bool FAST = decltype(fast_c)::value;
   for (int it = tid; it < items; it += kBlock) {
-    const int dn = (int)udiv((uint32_t)it, p.qd_magic);
-    const int c = (it - dn * (int)p.qd) * 4;
-    const int node = n0 + dn;
-    const int b = L.rowptr[dn], deg = L.rowptr[dn + 1] - b;
+    const BlkItem item = blk_item(p, L, n0, it);
+    const int dn = item.dn, c = item.c, node = item.node, b = item.b, deg = item.deg;
     if (deg > kGroupMaxDeg) continue;
-    Vec<4> su = vzero<4>();                                   // dL/dU[node]: the sum of the segment's message gradients, in position order
+    Vec<4> su = vzero<4>();                                  // dL/dU[node]: the sum of the segment's message gradients, in position order
     float m_b = 0.f;                                          // this item's share of the node's message-gradient bound
     if (deg > 0) {
       const float* cf = L.agg + (size_t)dn * NC * p.D + c;
@@ -1166,22 +1179,35 @@ static dim3 gr_grid(int64_t N, int D, int vec, int* lpr_log) {
   return dim3((unsigned)blocks, (unsigned)chunks);
 }
 
-// the flat kernels pay when segments are short on average (molecule batches); they leave segments above kGroupMaxDeg
-// edges to a wave-per-node pass.  Sets the flat geometry; false: run everything wave-per-node.
 static uint32_t div_magic(uint32_t d) { return d <= 1 ? 0u : (uint32_t)((1ULL << 32) / d) + 1u; }   // see udiv()
+
+// what the flat and the block kernels share on the host: the gate (both pay when segments are short on average - molecule
+// batches - and leave segments above kGroupMaxDeg edges to a wave-per-node pass), the item geometry and the grid
+static bool gr_short_segments(const GrParams& p, int64_t E) { return E <= 16 * (int64_t)p.N; }
+static void gr_set_items(GrParams* p, int nb, uint32_t qd) {   // nb nodes per workgroup, qd lanes (VEC columns each) per row
+  p->nb = nb; p->qd = qd;
+  p->qd_magic = div_magic(qd);                // exact floor(n / qd) for n, qd < 2^16
+  p->f_magic = div_magic((uint32_t)p->F);
+}
+// node blocks -> workgroup slots: a multiple of 8, so that slot % 8 is the XCD (flat_node_block), and at most `cap` (a multiple of 8:
+// the flat kernels stride over the slots, the block kernels need one workgroup per block)
+static dim3 gr_slot_grid(int64_t N, int nb, int64_t cap) {
+  const int64_t slots = ((N + nb - 1) / nb + 7) / 8 * 8;
+  return dim3((unsigned)(slots > cap ? cap : slots < 8 ? 8 : slots));
+}
+
+// Sets the flat geometry; false: run everything wave-per-node.
 constexpr int kFlatNodes = 16;       // nodes per workgroup: ZINC rows (95 quads) -> 1520 lanes of work, 5.9 sweeps of 256 threads
 static bool gr_flat_mode(GrParams* p, int64_t E, int vec) {
   const int qd = (p->D + vec - 1) / vec;
-  if (!(E <= 16 * (int64_t)p->N) || qd > 4095 || p->D > 65535) return false;
-  p->nb = kFlatNodes; p->qd = (uint32_t)qd;
-  p->qd_magic = div_magic((uint32_t)qd);      // exact floor(n / qd) for n, qd < 2^16
-  p->f_magic = div_magic((uint32_t)p->F);
+  if (!gr_short_segments(*p, E) || qd > 4095 || p->D > 65535) return false;
+  gr_set_items(p, kFlatNodes, (uint32_t)qd);
   return true;
 }
 // block kernels (fast path): vec4 operands, aggregators out of sum|mean|min|max only, short segments on average, and an LDS
 // budget that leaves several workgroups per CU.  Fills the geometry; returns the NEEDS mask, or 0 when the path does not apply.
 static int gr_block_mode(GrParams* p, int64_t E, bool v4, bool backward) {
-  if (!v4 || E <= 0 || !(E <= 16 * (int64_t)p->N) || p->mean || p->var || p->D > 16380 || p->F < 4) return 0;
+  if (!v4 || E <= 0 || !gr_short_segments(*p, E) || p->mean || p->var || p->D > 16380 || p->F < 4) return 0;
   if (backward && p->K * p->S > kBlkMaxKS) return 0;         // the backward loads all K*S gradient blocks of an item in one batch
   int needs = 0;
   for (int k = 0; k < p->K; ++k) {
@@ -1203,8 +1229,7 @@ static int gr_block_mode(GrParams* p, int64_t E, bool v4, bool backward) {
   for (int nb = nb_max; nb >= 2; nb >>= 1) {
     const uint32_t agg = (uint32_t)nb * planes * p->D * 4, arg = 2u * nb * p->D;
     if (head + agg + arg > 40 * 1024 || (uint32_t)nb * tskf4 > 65535u || (uint32_t)nb * qd > 65535u) continue;
-    p->nb = nb; p->qd = qd; p->qd_magic = div_magic(qd);
-    p->f_magic = div_magic((uint32_t)p->F);
+    gr_set_items(p, nb, qd);
     p->tskf4 = tskf4; p->m_tskf4 = div_magic(tskf4);
     p->skf4 = skf4; p->m_skf4 = div_magic(skf4);
     p->f4 = f4; p->m_f4 = div_magic(f4);
@@ -1214,31 +1239,58 @@ static int gr_block_mode(GrParams* p, int64_t E, bool v4, bool backward) {
   }
   return 0;
 }
-static dim3 gr_block_grid(const GrParams& p) {
-  const int64_t nblocks = ((int64_t)p.N + p.nb - 1) / p.nb;
-  return dim3((unsigned)((nblocks + 7) / 8 * 8));            // one workgroup per node block; a multiple of 8 (XCD slots)
+
+// ---- launches: run-time form -> template arguments (with_flag of common.h).  BWD = false: K3, true: K4.  The block kernel: exactly the
+// forms that exist are instantiated (given messages have neither Z nor dropout, the backward no HASZ, NEEDS is one of two masks).
+template <bool BWD>
+static void gr_launch_block(const GrParams& p, int needs, hipStream_t st) {
+  const dim3 grid = gr_slot_grid(p.N, p.nb, INT64_MAX);       // one workgroup per node block
+  const bool fused = p.inputs == nullptr;
+  with_flag(!fused, [&](auto given) { with_flag(!BWD && fused && p.Z, [&](auto hz) {
+    with_flag(fused && p.drop.mode != MMA_DROP_NONE, [&](auto dr) { with_flag(needs == (NEED_MIN | NEED_MAX), [&](auto mm) {
+      constexpr bool FUSED = !decltype(given)::value, HASZ = decltype(hz)::value, DROP = decltype(dr)::value;
+      constexpr int NEEDS = decltype(mm)::value ? (NEED_MIN | NEED_MAX) : (NEED_SUM | NEED_MIN | NEED_MAX);
+      if constexpr (FUSED || !(DROP || HASZ)) {
+        if constexpr (BWD) hipLaunchKernelGGL((gr_bwd_block_kernel<FUSED, DROP, NEEDS>), grid, dim3(kBlock), p.lds_bytes, st, p);
+        else hipLaunchKernelGGL((gr_fwd_block_kernel<FUSED, HASZ, DROP, NEEDS>), grid, dim3(kBlock), p.lds_bytes, st, p);
+      }
+    }); });
+  }); });
 }
 
-template <bool FUSED, bool HASZ, bool DROP>
-static void launch_fwd_block(int needs, dim3 grid, unsigned lds, hipStream_t st, const GrParams& p) {
-  if (needs == (NEED_MIN | NEED_MAX))
-    hipLaunchKernelGGL((gr_fwd_block_kernel<FUSED, HASZ, DROP, NEED_MIN | NEED_MAX>), grid, dim3(kBlock), lds, st, p);
-  else
-    hipLaunchKernelGGL((gr_fwd_block_kernel<FUSED, HASZ, DROP, NEED_SUM | NEED_MIN | NEED_MAX>), grid, dim3(kBlock), lds, st, p);
+// the generic kernels of a direction, by form, and their launch at VEC = 4 or 1
+enum { GR_WAVE, GR_LIST, GR_FLAT };
+template <bool BWD, int FORM, int VEC> static auto gr_kernel() {
+  if constexpr (FORM == GR_FLAT) { if constexpr (BWD) return gr_bwd_flat_kernel<VEC>; else return gr_fwd_flat_kernel<VEC>; }
+  else if constexpr (FORM == GR_LIST) { if constexpr (BWD) return gr_bwd_list_kernel<VEC>; else return gr_fwd_list_kernel<VEC>; }
+  else { if constexpr (BWD) return gr_bwd_kernel<VEC>; else return gr_fwd_kernel<VEC>; }
 }
-template <bool FUSED, bool DROP>
-static void launch_bwd_block(int needs, dim3 grid, unsigned lds, hipStream_t st, const GrParams& p) {
-  if (needs == (NEED_MIN | NEED_MAX))
-    hipLaunchKernelGGL((gr_bwd_block_kernel<FUSED, DROP, NEED_MIN | NEED_MAX>), grid, dim3(kBlock), lds, st, p);
-  else
-    hipLaunchKernelGGL((gr_bwd_block_kernel<FUSED, DROP, NEED_SUM | NEED_MIN | NEED_MAX>), grid, dim3(kBlock), lds, st, p);
+template <bool BWD, int FORM>
+static int gr_start(const char* what, bool v4, dim3 grid, hipStream_t st, const GrParams& p) {
+  with_flag(v4, [&](auto v) { hipLaunchKernelGGL((gr_kernel<BWD, FORM, decltype(v)::value ? 4 : 1>()), grid, dim3(kBlock), 0, st, p); });
+  return check_launch(what);
 }
 
-static dim3 gr_flat_grid(int64_t N) {
-  int64_t slots = ((N + kFlatNodes - 1) / kFlatNodes + 7) / 8 * 8;
-  if (slots > 4 * kMaxGrid) slots = 4 * kMaxGrid;                    // a multiple of 8: grid-stride keeps a slot's XCD
-  if (slots < 8) slots = 8;
-  return dim3((unsigned)slots);
+// Every launch of one call.  The molecule-batch shape takes the two-phase block kernel (block_ok: not with var / std in the backward),
+// other short-segment graphs the flat kernel; then the wave-per-node pass: everything (with no edge at all it writes the empty results),
+// or - behind a block / flat kernel - the segments above kGroupMaxDeg edges only, taken from the list mma_build_csr made when the
+// caller has one (an empty list costs one trivial launch instead of a scan of N).
+template <bool BWD>
+static int gr_launch(GrParams& p, int64_t E, bool v4, bool block_ok, void* stream) {
+  const dim3 grid = gr_grid(p.N, p.D, v4 ? 4 : 1, &p.lpr_log);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (const int needs = block_ok ? gr_block_mode(&p, E, v4, BWD) : 0) {
+    gr_launch_block<BWD>(p, needs, st);
+    if (int rc = check_launch(BWD ? "gr_bwd_block_kernel" : "gr_fwd_block_kernel")) return rc;
+    p.wave_min_deg = kGroupMaxDeg + 1;
+  } else if (E > 0 && gr_flat_mode(&p, E, v4 ? 4 : 1)) {
+    const dim3 fg = gr_slot_grid(p.N, kFlatNodes, 4 * kMaxGrid);
+    if (int rc = gr_start<BWD, GR_FLAT>(BWD ? "gr_bwd_flat_kernel" : "gr_fwd_flat_kernel", v4, fg, st, p)) return rc;
+    p.wave_min_deg = kGroupMaxDeg + 1;
+  }
+  if (p.wave_min_deg > 0 && p.long_nodes)
+    return gr_start<BWD, GR_LIST>(BWD ? "gr_bwd_list_kernel" : "gr_fwd_list_kernel", v4, dim3(128, grid.y), st, p);
+  return gr_start<BWD, GR_WAVE>(BWD ? "gr_bwd_kernel" : "gr_fwd_kernel", v4, grid, st, p);
 }
 
 }  // namespace mma
@@ -1296,22 +1348,39 @@ extern "C" int mma_build_csr(const int64_t* key, const int64_t* other, int64_t E
 
 extern "C" int64_t mma_gr_arg_side_rows(int64_t E) { return E < 0 ? -1 : (E >> 8) + 2; }
 
+// ---- what the two entry points share, in the order they have always made their checks: gr_open, the entry point's own checks,
+// gr_fill_common, the entry point's own outputs, gr_launch
+static int gr_open(GrParams& p, int64_t N, int64_t E, int32_t T, int32_t F, const uint8_t* aggr_host, int32_t K,
+                   const uint8_t* scaler_host, int32_t S, const int32_t* long_nodes) {
+  MMA_REQUIRE(N >= 0 && E >= 0 && N < (1LL << 31) - (1 << 20) && E < (1LL << 31) && T >= 1 && F >= 1 && (int64_t)T * F < (1 << 24),
+              "N=%lld E=%lld T=%d F=%d unsupported", (long long)N, (long long)E, T, F);
+  if (int rc = fill_codes(aggr_host, K, scaler_host, S, &p)) return rc;
+  p.long_nodes = long_nodes;
+  p.long_cap = (int)min((int64_t)0x7fffffff, E / (kGroupMaxDeg + 1) + 1);
+  return 0;
+}
+
 static int gr_fill_common(GrParams& p, const int32_t* rowptr, const int32_t* src, const int32_t* perm, const float* U, const float* V,
-                          int64_t lduv, const float* Z, int64_t ldz, int32_t by_pos, const float* inputs, int64_t ldi,
-                          uint8_t* amin8, uint8_t* amax8, int32_t* amin_side, int32_t* amax_side, float* mean, float* var,
-                          int64_t ldsave, int64_t N, int64_t E, int32_t T, int32_t F, float avg_log, float avg_lin, int32_t drop_mode,
-                          uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev) {
+                          int64_t lduv, const float* Z, int64_t ldz, int32_t by_pos, const uint8_t* z_index, const float* inputs,
+                          int64_t ldi, const uint8_t* amin8, const uint8_t* amax8, const int32_t* amin_side, const int32_t* amax_side,
+                          const float* mean, const float* var, int64_t ldsave, int64_t N, int64_t E, int32_t T, int32_t F, float avg_log,
+                          float avg_lin, int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev) {
   MMA_REQUIRE(drop_mode == MMA_DROP_NONE || drop_mode == MMA_DROP_HASH, "GR dropout: NONE or HASH");
   MMA_REQUIRE(drop_mode == MMA_DROP_NONE || drop_thr < 65536, "drop_thr out of range (0..65535: P(drop) = thr / 65536)");
   MMA_REQUIRE((amin8 == nullptr) == (amin_side == nullptr) && (amax8 == nullptr) == (amax_side == nullptr),
               "arg8 (N,ldsave) bytes and arg_side (mma_gr_arg_side_rows(E), ldsave) int32 come in pairs");
   p.rowptr = rowptr; p.src = src; p.perm = perm; p.U = U; p.V = V; p.lduv = lduv; p.Z = Z; p.ldz = ldz; p.by_pos = by_pos ? 1 : 0;
-  p.inputs = inputs; p.ldi = ldi; p.amin8 = amin8; p.amax8 = amax8; p.amin_side = amin_side; p.amax_side = amax_side;
-  p.mean = mean; p.var = var; p.ldsave = ldsave;
+  p.inputs = inputs; p.ldi = ldi;
+  // the saved state: written by K3, read by K4
+  p.amin8 = const_cast<uint8_t*>(amin8); p.amax8 = const_cast<uint8_t*>(amax8);
+  p.amin_side = const_cast<int32_t*>(amin_side); p.amax_side = const_cast<int32_t*>(amax_side);
+  p.mean = const_cast<float*>(mean); p.var = const_cast<float*>(var); p.ldsave = ldsave;
   p.N = (int)N; p.D = T * F; p.T = T; p.F = F; p.avg_log = avg_log; p.avg_lin = avg_lin;
   drop_set_threshold(&p.drop, (drop_mode == MMA_DROP_HASH && drop_thr > 0 && !inputs) ? MMA_DROP_HASH : MMA_DROP_NONE, drop_thr);
   p.drop.seed_lo = (uint32_t)seed; p.drop.seed_hi = (uint32_t)(seed >> 32); p.drop.seed_dev = seed_dev; p.drop.keep = nullptr;
   p.drop.E = E; p.drop.edge_base = 0;
+  MMA_REQUIRE(!z_index || Z, "z_index without a Z table");
+  p.zidx = z_index;
   return 0;
 }
 
@@ -1323,12 +1392,8 @@ extern "C" int mma_gr_fused_fwd(
     const int32_t* long_nodes,
     int64_t N, int64_t E, int32_t T, int32_t F, const uint8_t* aggr_host, int32_t K, const uint8_t* scaler_host, int32_t S,
     float avg_log, float avg_lin, int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, void* stream) {
-  MMA_REQUIRE(N >= 0 && E >= 0 && N < (1LL << 31) - (1 << 20) && E < (1LL << 31) && T >= 1 && F >= 1 && (int64_t)T * F < (1 << 24),
-              "N=%lld E=%lld T=%d F=%d unsupported", (long long)N, (long long)E, T, F);
   GrParams p{};
-  if (int rc = fill_codes(aggr_host, K, scaler_host, S, &p)) return rc;
-  p.long_nodes = long_nodes;
-  p.long_cap = (int)min((int64_t)0x7fffffff, E / (kGroupMaxDeg + 1) + 1);
+  if (int rc = gr_open(p, N, E, T, F, aggr_host, K, scaler_host, S, long_nodes)) return rc;
   if (N == 0) return 0;
   const int D = T * F;
   MMA_REQUIRE(rowptr && out, "NULL argument");
@@ -1339,41 +1404,10 @@ extern "C" int mma_gr_fused_fwd(
   MMA_REQUIRE((inputs != nullptr) != (U != nullptr && V != nullptr), "give either `inputs` or U and V");
   MMA_REQUIRE(inputs ? ldi >= D : (lduv >= D && (!Z || ldz >= D)), "row pitch too small");
   MMA_REQUIRE(!(amin8 || amax8 || mean || var) || ldsave >= D, "ldsave=%lld < T*F", (long long)ldsave);
-  if (int rc = gr_fill_common(p, rowptr, src, perm, U, V, lduv, Z, ldz, by_pos, inputs, ldi, amin8, amax8, amin_side, amax_side, mean,
-                              var, ldsave, N, E, T, F, avg_log, avg_lin, drop_mode, drop_thr, seed, seed_dev)) return rc;
-  MMA_REQUIRE(!z_index || Z, "z_index without a Z table");
-  p.zidx = z_index;
+  if (int rc = gr_fill_common(p, rowptr, src, perm, U, V, lduv, Z, ldz, by_pos, z_index, inputs, ldi, amin8, amax8, amin_side, amax_side,
+                              mean, var, ldsave, N, E, T, F, avg_log, avg_lin, drop_mode, drop_thr, seed, seed_dev)) return rc;
   p.out = out;
-  const bool v4 = gr_vec4(p);
-  const dim3 grid = gr_grid(N, D, v4 ? 4 : 1, &p.lpr_log);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool drop = p.drop.mode != MMA_DROP_NONE;
-  if (E == 0) {                                                   // no edge: the plain wave-per-node kernel writes the empty results
-  } else if (const int needs = gr_block_mode(&p, E, v4, false)) { // molecule-batch shape: two-phase block kernel
-    const dim3 bg = gr_block_grid(p);
-    if (inputs) launch_fwd_block<false, false, false>(needs, bg, p.lds_bytes, st, p);
-    else if (Z) { if (drop) launch_fwd_block<true, true, true>(needs, bg, p.lds_bytes, st, p); else launch_fwd_block<true, true, false>(needs, bg, p.lds_bytes, st, p); }
-    else { if (drop) launch_fwd_block<true, false, true>(needs, bg, p.lds_bytes, st, p); else launch_fwd_block<true, false, false>(needs, bg, p.lds_bytes, st, p); }
-    if (int rc = check_launch("gr_fwd_block_kernel")) return rc;
-    p.wave_min_deg = kGroupMaxDeg + 1;
-  } else if (gr_flat_mode(&p, E, v4 ? 4 : 1)) {      // short segments, generic form: flat kernel
-    const dim3 fg = gr_flat_grid(N);
-    if (v4) hipLaunchKernelGGL((gr_fwd_flat_kernel<4>), fg, dim3(kBlock), 0, st, p);
-    else hipLaunchKernelGGL((gr_fwd_flat_kernel<1>), fg, dim3(kBlock), 0, st, p);
-    if (int rc = check_launch("gr_fwd_flat_kernel")) return rc;
-    p.wave_min_deg = kGroupMaxDeg + 1;
-  }
-  // the wave-per-node pass: everything, or - behind a block / flat kernel - the segments above kGroupMaxDeg edges only, taken
-  // from the list mma_build_csr made when the caller has one (an empty list costs one trivial launch instead of a scan of N)
-  if (p.wave_min_deg > 0 && long_nodes) {
-    const dim3 lg(128, grid.y);
-    if (v4) hipLaunchKernelGGL((gr_fwd_list_kernel<4>), lg, dim3(kBlock), 0, st, p);
-    else hipLaunchKernelGGL((gr_fwd_list_kernel<1>), lg, dim3(kBlock), 0, st, p);
-    return check_launch("gr_fwd_list_kernel");
-  }
-  if (v4) hipLaunchKernelGGL((gr_fwd_kernel<4>), grid, dim3(kBlock), 0, st, p);
-  else hipLaunchKernelGGL((gr_fwd_kernel<1>), grid, dim3(kBlock), 0, st, p);
-  return check_launch("gr_fwd_kernel");
+  return gr_launch<false>(p, E, gr_vec4(p), true, stream);
 }
 
 extern "C" int mma_gr_fused_bwd(
@@ -1385,59 +1419,24 @@ extern "C" int mma_gr_fused_bwd(
     float* gmsg_row_max, float* gu_row_max,
     int64_t N, int64_t E, int32_t T, int32_t F, const uint8_t* aggr_host, int32_t K, const uint8_t* scaler_host, int32_t S,
     float avg_log, float avg_lin, int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, void* stream) {
-  MMA_REQUIRE(N >= 0 && E >= 0 && N < (1LL << 31) - (1 << 20) && E < (1LL << 31) && T >= 1 && F >= 1 && (int64_t)T * F < (1 << 24),
-              "N=%lld E=%lld T=%d F=%d unsupported", (long long)N, (long long)E, T, F);
   GrParams p{};
-  if (int rc = fill_codes(aggr_host, K, scaler_host, S, &p)) return rc;
-  p.long_nodes = long_nodes;
-  p.long_cap = (int)min((int64_t)0x7fffffff, E / (kGroupMaxDeg + 1) + 1);
+  if (int rc = gr_open(p, N, E, T, F, aggr_host, K, scaler_host, S, long_nodes)) return rc;
   MMA_REQUIRE((gmsg_row_max == nullptr) == (gu_row_max == nullptr) && (!gu_row_max || gU), "the row maxima come as a pair, with gU");
   if (N == 0 || E == 0) return 0;
   const int D = T * F;
   MMA_REQUIRE(rowptr && src && perm && gout && gmsg && ldg >= D, "NULL argument or pitch too small");
   p.gmsg_rmax = reinterpret_cast<uint32_t*>(gmsg_row_max); p.gu_rmax = reinterpret_cast<uint32_t*>(gu_row_max);
-  bool need_min = false, need_max = false, need_stats = false;
-  for (int k = 0; k < K; ++k) {
-    need_min |= p.aggr[k] == GR_MIN; need_max |= p.aggr[k] == GR_MAX; need_stats |= p.aggr[k] >= GR_VAR;
-  }
-  MMA_REQUIRE((!need_min || amin8) && (!need_max || amax8) && (!need_stats || (mean && var)), "saved forward state missing");
+  const bool need_stats = p.need_sq;                              // var / std in the aggregator list (fill_codes)
+  MMA_REQUIRE((!p.need_min || amin8) && (!p.need_max || amax8) && (!need_stats || (mean && var)), "saved forward state missing");
   MMA_REQUIRE(!need_stats || (inputs != nullptr) != (U != nullptr && V != nullptr), "var/std backward needs the messages");
   MMA_REQUIRE(!gU || ldgu >= D, "ldgu=%lld < T*F", (long long)ldgu);
-  MMA_REQUIRE(!(need_min || need_max || need_stats) || ldsave >= D, "ldsave=%lld < T*F", (long long)ldsave);
-  if (int rc = gr_fill_common(p, rowptr, src, perm, U, V, lduv, Z, ldz, by_pos, inputs, ldi,
-                              const_cast<uint8_t*>(need_min ? amin8 : nullptr), const_cast<uint8_t*>(need_max ? amax8 : nullptr),
-                              const_cast<int32_t*>(need_min ? amin_side : nullptr), const_cast<int32_t*>(need_max ? amax_side : nullptr),
-                              const_cast<float*>(mean), const_cast<float*>(var), ldsave, N, E, T, F, avg_log, avg_lin, drop_mode,
-                              drop_thr, seed, seed_dev)) return rc;
-  MMA_REQUIRE(!z_index || Z, "z_index without a Z table");
-  p.zidx = z_index;
+  MMA_REQUIRE(!(p.need_min || p.need_max || need_stats) || ldsave >= D, "ldsave=%lld < T*F", (long long)ldsave);
+  // saved args the aggregator list does not use are not passed on
+  if (int rc = gr_fill_common(p, rowptr, src, perm, U, V, lduv, Z, ldz, by_pos, z_index, inputs, ldi, p.need_min ? amin8 : nullptr,
+                              p.need_max ? amax8 : nullptr, p.need_min ? amin_side : nullptr, p.need_max ? amax_side : nullptr, mean, var,
+                              ldsave, N, E, T, F, avg_log, avg_lin, drop_mode, drop_thr, seed, seed_dev)) return rc;
   p.gout = gout; p.gmsg = gmsg; p.ldg = ldg; p.gU = gU; p.ldgu = ldgu;
   const bool v4 = gr_vec4(p) && ldg % 4 == 0 && (reinterpret_cast<uintptr_t>(gmsg) & 15) == 0 &&
                   (!gU || (ldgu % 4 == 0 && (reinterpret_cast<uintptr_t>(gU) & 15) == 0));
-  const dim3 grid = gr_grid(N, D, v4 ? 4 : 1, &p.lpr_log);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool drop = p.drop.mode != MMA_DROP_NONE;
-  if (const int needs = need_stats ? 0 : gr_block_mode(&p, E, v4, true)) {
-    const dim3 bg = gr_block_grid(p);
-    if (inputs) launch_bwd_block<false, false>(needs, bg, p.lds_bytes, st, p);
-    else if (drop) launch_bwd_block<true, true>(needs, bg, p.lds_bytes, st, p);
-    else launch_bwd_block<true, false>(needs, bg, p.lds_bytes, st, p);
-    if (int rc = check_launch("gr_bwd_block_kernel")) return rc;
-    p.wave_min_deg = kGroupMaxDeg + 1;
-  } else if (gr_flat_mode(&p, E, v4 ? 4 : 1)) {
-    const dim3 fg = gr_flat_grid(N);
-    if (v4) hipLaunchKernelGGL((gr_bwd_flat_kernel<4>), fg, dim3(kBlock), 0, st, p);
-    else hipLaunchKernelGGL((gr_bwd_flat_kernel<1>), fg, dim3(kBlock), 0, st, p);
-    if (int rc = check_launch("gr_bwd_flat_kernel")) return rc;
-    p.wave_min_deg = kGroupMaxDeg + 1;
-  }
-  if (p.wave_min_deg > 0 && long_nodes) {
-    const dim3 lg(128, grid.y);
-    if (v4) hipLaunchKernelGGL((gr_bwd_list_kernel<4>), lg, dim3(kBlock), 0, st, p);
-    else hipLaunchKernelGGL((gr_bwd_list_kernel<1>), lg, dim3(kBlock), 0, st, p);
-    return check_launch("gr_bwd_list_kernel");
-  }
-  if (v4) hipLaunchKernelGGL((gr_bwd_kernel<4>), grid, dim3(kBlock), 0, st, p);
-  else hipLaunchKernelGGL((gr_bwd_kernel<1>), grid, dim3(kBlock), 0, st, p);
-  return check_launch("gr_bwd_kernel");
+  return gr_launch<true>(p, E, v4, !need_stats, stream);
 }

@@ -891,7 +891,7 @@ __global__ __launch_bounds__(kBlock, (K <= 4 ? MMA_MIN_WAVES : 1)) void nc_bwd_s
 }
 
 // ------------------------------------------------------------------------------------------------------
-// host side: what is specific to K1 / K2a / K2b; the checks, make_drop, geometry, the grids and with_flag / with_dm are in nc_shared.h
+// host side: what is specific to K1 / K2a / K2b; the checks, make_drop, geometry, the grids and with_dm are in nc_shared.h, ic / with_flag in common.h
 static int pack_codes(const uint8_t* kind_host, const uint8_t* act_host, int K, uint32_t* kinds, uint32_t* acts) {
   *kinds = 0; *acts = 0;
   for (int k = 0; k < K; ++k) {
@@ -918,7 +918,7 @@ static int64_t fill_sel_slots(const uint8_t* kind_host, int K, int H, uint32_t* 
   return ((4 + (int64_t)n * (((int64_t)H + 3) / 4)) + 3) & ~(int64_t)3;      // 64-bit: H comes straight from the caller
 }
 
-// run-time value -> template argument, beside with_flag / with_dm of nc_shared.h.  Only what the kernels are instantiated for is
+// run-time value -> template argument, beside with_flag of common.h and with_dm of nc_shared.h.  Only what the kernels are instantiated for is
 // reachable: K-slices {1,2,3,4,8}; the one-launch kernels do not exist for explicit masks (with_dm<false>: small_plan refuses
 // them); nc_bwd_kernel has no <SHARED = false, EPI = true> (launch_bwd).
 template <class F> static void with_k(int Ks, F&& f) {

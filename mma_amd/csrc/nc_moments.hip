@@ -432,7 +432,7 @@ __global__ __launch_bounds__(kBlock) void nc_std_bwd_finalize_kernel(const NcStd
 }
 
 // ------------------------------------------------------------------------------------------------------
-// host side: what is specific to K1s / K2s; the checks, make_drop, geometry, the grids and with_flag / with_dm are in nc_shared.h
+// host side: what is specific to K1s / K2s; the checks, make_drop, geometry, the grids and with_dm are in nc_shared.h, with_flag in common.h
 // a bf16 table at an odd address cannot be read at all (the scalar form loads 2-byte elements); fp32 tables are taken as they always were
 template <class TT> static int std_table_checks(const TT* P, const TT* Q) {
   MMA_REQUIRE(sizeof(TT) != 2 || ((reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(Q)) & 1u) == 0,

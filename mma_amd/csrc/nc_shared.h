@@ -76,10 +76,8 @@ static dim3 elementwise_grid(int64_t total) {
   return dim3((unsigned)(b < 1 ? 1 : (b > kMaxGrid * 4 ? kMaxGrid * 4 : b)));
 }
 
-// run-time value -> template argument: f receives it as a std::integral_constant (a generic lambda reads decltype(v)::value).
+// run-time dropout mode -> template argument, beside ic / with_flag of common.h.
 // EXPLICIT_OK = false: for kernels that are not instantiated for explicit masks (the one-launch kernels of nc_fused.hip).
-template <int V> using ic = std::integral_constant<int, V>;
-template <class F> static void with_flag(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 template <bool EXPLICIT_OK = true, class F> static void with_dm(int dm, F&& f) {
   if (dm == MMA_DROP_HASH) f(ic<MMA_DROP_HASH>{});
   else if (dm == MMA_DROP_HASH16) f(ic<MMA_DROP_HASH16>{});
