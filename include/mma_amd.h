@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MMA_ABI_VERSION 41
+#define MMA_ABI_VERSION 42
 #define MMA_MAX_K 8          /* masks fused per launch; more are issued as several launches */
 
 /* combine kinds of the node-classification aggregators (layers.py:201-728) */
@@ -643,6 +643,30 @@ int mma_gr_fused_bwd(
     float* gmsg_row_max, float* gu_row_max,
     int64_t N, int64_t E, int32_t T, int32_t F, const uint8_t* aggr_host, int32_t K, const uint8_t* scaler_host, int32_t S,
     float avg_log, float avg_lin, int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, void* stream);
+
+/* ---- the plan of a K3 / K4 call (ABI 42): which kernels mma_gr_fused_fwd (backward == 0) or mma_gr_fused_bwd would launch --------------
+ * Host only: nothing launches and no device pointer is taken.  The arguments are what the launch ladder reads ("The GR
+ * launch ladder"): the shape and the code lists of the call; its row pitches, 0 = the operand is absent (lduv: U and V; ldz: Z; ldi:
+ * inputs; ldsave: the saved args - and mean / var with has_stats; ldg: gmsg; ldgu: gU; ldg and ldgu are 0 for a forward); and flags:
+ * has_z, given (messages given as `inputs`, not formed from U, V, Z), has_stats (mean and var are passed), has_list (long_nodes is
+ * passed), drop_on, aligned (every base address is a multiple of 16 bytes).  The environment variable MMA_GR_NB caps nb as it does
+ * for the call itself.  plan_host: MMA_GR_PLAN_WORDS int32 of HOST memory, all 0 for a call that launches nothing (N == 0, a backward
+ * with E == 0):
+ *   [0] first pass      0 none (the wave-per-node kernel alone), 1 flat kernel, 2 block kernel
+ *   [1] VEC             4 (16-byte row access) or 1
+ *   [2] nb              nodes per workgroup of the first pass (0 without one)
+ *   [3] NEEDS           the block kernel's instantiation: 6 {min,max}, 7 {sum,min,max}; 0 otherwise
+ *   [4] lpr_log         wave-per-node and list kernels: log2 of the lanes that share one row
+ *   [5] column chunks   their grid.y
+ *   [6] second pass     0 none, 1 wave-per-node over every node, 2 wave-per-node over the segments above MMA_GR_LONG_SEGMENT edges
+ *                       (a scan of all row pointers), 3 the same segments from the long_nodes list
+ *   [7] lds_bytes       dynamic LDS of the block kernel (0 otherwise)
+ * What the entry point of the direction checks of these arguments is checked here too, under the same conditions: a forward with a
+ * pitch below T*F is refused, not planned; a backward is refused for ldg, ldgu and the ldsave its aggregators need. */
+#define MMA_GR_PLAN_WORDS 8
+int mma_gr_plan(int64_t N, int64_t E, int32_t T, int32_t F, const uint8_t* aggr_host, int32_t K, const uint8_t* scaler_host, int32_t S,
+                int32_t backward, int64_t lduv, int64_t ldz, int64_t ldi, int64_t ldsave, int64_t ldg, int64_t ldgu,
+                int32_t has_z, int32_t given, int32_t has_stats, int32_t has_list, int32_t drop_on, int32_t aligned, int32_t* plan_host);
 
 #ifdef __cplusplus
 }

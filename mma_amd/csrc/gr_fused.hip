@@ -1271,26 +1271,54 @@ static int gr_start(const char* what, bool v4, dim3 grid, hipStream_t st, const 
   return check_launch(what);
 }
 
-// Every launch of one call.  The molecule-batch shape takes the two-phase block kernel (block_ok: not with var / std in the backward),
-// other short-segment graphs the flat kernel; then the wave-per-node pass: everything (with no edge at all it writes the empty results),
-// or - behind a block / flat kernel - the segments above kGroupMaxDeg edges only, taken from the list mma_build_csr made when the
-// caller has one (an empty list costs one trivial launch instead of a scan of N).
+// 16-byte access in the backward: what gr_vec4 asks of the forward's operands, and the same of gmsg and gU
+static bool gr_vec4_bwd(const GrParams& p) {
+  return gr_vec4(p) && p.ldg % 4 == 0 && (reinterpret_cast<uintptr_t>(p.gmsg) & 15) == 0 &&
+         (!p.gU || (p.ldgu % 4 == 0 && (reinterpret_cast<uintptr_t>(p.gU) & 15) == 0));
+}
+// calls that launch nothing: no node, or a backward with no edge (there is no gradient row to write)
+static bool gr_nothing_to_do(int64_t N, int64_t E, bool backward) { return N == 0 || (backward && E == 0); }
+
+// Every launch of one call, decided on the host from the filled GrParams alone (mma_gr_plan reports exactly this).  The molecule-batch
+// shape takes the two-phase block kernel (not with var / std in the backward), other short-segment graphs the flat kernel; then the
+// wave-per-node pass: everything (with no edge at all it writes the empty results), or - behind a block / flat kernel - the segments
+// above kGroupMaxDeg edges only, taken from the list mma_build_csr made when the caller has one (an empty list costs one trivial
+// launch instead of a scan of N).
+enum { PLAN_NONE = 0, PLAN_FLAT = 1, PLAN_BLOCK = 2 };               // first pass
+enum { PLAN_WAVE_ALL = 1, PLAN_WAVE_LONG = 2, PLAN_LIST = 3 };       // second pass (0: nothing launches)
+struct GrPlan { int first, vec, nb, needs, lpr_log, chunks, second, lds_bytes; dim3 grid; };
+static GrPlan gr_plan(GrParams& p, int64_t E, bool backward) {
+  GrPlan pl{};
+  const bool v4 = backward ? gr_vec4_bwd(p) : gr_vec4(p);
+  const bool block_ok = !(backward && p.need_sq);                   // var / std in the aggregator list (fill_codes)
+  pl.vec = v4 ? 4 : 1;
+  pl.grid = gr_grid(p.N, p.D, pl.vec, &p.lpr_log);
+  pl.lpr_log = p.lpr_log; pl.chunks = (int)pl.grid.y;
+  if (const int needs = block_ok ? gr_block_mode(&p, E, v4, backward) : 0) {
+    pl.first = PLAN_BLOCK; pl.needs = needs; pl.nb = p.nb; pl.lds_bytes = (int)p.lds_bytes;
+  } else if (E > 0 && gr_flat_mode(&p, E, pl.vec)) {
+    pl.first = PLAN_FLAT; pl.nb = p.nb;
+  }
+  if (pl.first != PLAN_NONE) p.wave_min_deg = kGroupMaxDeg + 1;
+  pl.second = p.wave_min_deg > 0 ? (p.long_nodes ? PLAN_LIST : PLAN_WAVE_LONG) : PLAN_WAVE_ALL;
+  return pl;
+}
+
 template <bool BWD>
-static int gr_launch(GrParams& p, int64_t E, bool v4, bool block_ok, void* stream) {
-  const dim3 grid = gr_grid(p.N, p.D, v4 ? 4 : 1, &p.lpr_log);
+static int gr_launch(GrParams& p, int64_t E, void* stream) {
+  const GrPlan pl = gr_plan(p, E, BWD);
+  const bool v4 = pl.vec == 4;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (const int needs = block_ok ? gr_block_mode(&p, E, v4, BWD) : 0) {
-    gr_launch_block<BWD>(p, needs, st);
+  if (pl.first == PLAN_BLOCK) {
+    gr_launch_block<BWD>(p, pl.needs, st);
     if (int rc = check_launch(BWD ? "gr_bwd_block_kernel" : "gr_fwd_block_kernel")) return rc;
-    p.wave_min_deg = kGroupMaxDeg + 1;
-  } else if (E > 0 && gr_flat_mode(&p, E, v4 ? 4 : 1)) {
+  } else if (pl.first == PLAN_FLAT) {
     const dim3 fg = gr_slot_grid(p.N, kFlatNodes, 4 * kMaxGrid);
     if (int rc = gr_start<BWD, GR_FLAT>(BWD ? "gr_bwd_flat_kernel" : "gr_fwd_flat_kernel", v4, fg, st, p)) return rc;
-    p.wave_min_deg = kGroupMaxDeg + 1;
   }
-  if (p.wave_min_deg > 0 && p.long_nodes)
-    return gr_start<BWD, GR_LIST>(BWD ? "gr_bwd_list_kernel" : "gr_fwd_list_kernel", v4, dim3(128, grid.y), st, p);
-  return gr_start<BWD, GR_WAVE>(BWD ? "gr_bwd_kernel" : "gr_fwd_kernel", v4, grid, st, p);
+  if (pl.second == PLAN_LIST)
+    return gr_start<BWD, GR_LIST>(BWD ? "gr_bwd_list_kernel" : "gr_fwd_list_kernel", v4, dim3(128, pl.grid.y), st, p);
+  return gr_start<BWD, GR_WAVE>(BWD ? "gr_bwd_kernel" : "gr_fwd_kernel", v4, pl.grid, st, p);
 }
 
 }  // namespace mma
@@ -1348,6 +1376,12 @@ extern "C" int mma_build_csr(const int64_t* key, const int64_t* other, int64_t E
 
 extern "C" int64_t mma_gr_arg_side_rows(int64_t E) { return E < 0 ? -1 : (E >> 8) + 2; }
 
+// the pitch conditions of K3, K4 and mma_gr_plan (each states them with its own operands; the refusal texts stay at the call sites)
+static bool gr_msg_pitches_ok(bool given, bool has_z, int D, int64_t ldi, int64_t lduv, int64_t ldz) {
+  return given ? ldi >= D : (lduv >= D && (!has_z || ldz >= D));
+}
+static bool gr_opt_pitch_ok(bool present, int D, int64_t ld) { return !present || ld >= D; }     // ldsave with saved state, ldgu with gU
+
 // ---- what the two entry points share, in the order they have always made their checks: gr_open, the entry point's own checks,
 // gr_fill_common, the entry point's own outputs, gr_launch
 static int gr_open(GrParams& p, int64_t N, int64_t E, int32_t T, int32_t F, const uint8_t* aggr_host, int32_t K,
@@ -1394,7 +1428,7 @@ extern "C" int mma_gr_fused_fwd(
     float avg_log, float avg_lin, int32_t drop_mode, uint32_t drop_thr, uint64_t seed, const uint64_t* seed_dev, void* stream) {
   GrParams p{};
   if (int rc = gr_open(p, N, E, T, F, aggr_host, K, scaler_host, S, long_nodes)) return rc;
-  if (N == 0) return 0;
+  if (gr_nothing_to_do(N, E, false)) return 0;
   const int D = T * F;
   MMA_REQUIRE(rowptr && out, "NULL argument");
   MMA_REQUIRE(E == 0 || (src && perm), "NULL CSR arrays");
@@ -1402,12 +1436,12 @@ extern "C" int mma_gr_fused_fwd(
     inputs = out; ldi = D;                   // read; the pointer only selects the form (every target is empty: 0, or sqrt(eps) for std)
   }
   MMA_REQUIRE((inputs != nullptr) != (U != nullptr && V != nullptr), "give either `inputs` or U and V");
-  MMA_REQUIRE(inputs ? ldi >= D : (lduv >= D && (!Z || ldz >= D)), "row pitch too small");
-  MMA_REQUIRE(!(amin8 || amax8 || mean || var) || ldsave >= D, "ldsave=%lld < T*F", (long long)ldsave);
+  MMA_REQUIRE(gr_msg_pitches_ok(inputs != nullptr, Z != nullptr, D, ldi, lduv, ldz), "row pitch too small");
+  MMA_REQUIRE(gr_opt_pitch_ok(amin8 || amax8 || mean || var, D, ldsave), "ldsave=%lld < T*F", (long long)ldsave);
   if (int rc = gr_fill_common(p, rowptr, src, perm, U, V, lduv, Z, ldz, by_pos, z_index, inputs, ldi, amin8, amax8, amin_side, amax_side,
                               mean, var, ldsave, N, E, T, F, avg_log, avg_lin, drop_mode, drop_thr, seed, seed_dev)) return rc;
   p.out = out;
-  return gr_launch<false>(p, E, gr_vec4(p), true, stream);
+  return gr_launch<false>(p, E, stream);
 }
 
 extern "C" int mma_gr_fused_bwd(
@@ -1422,21 +1456,66 @@ extern "C" int mma_gr_fused_bwd(
   GrParams p{};
   if (int rc = gr_open(p, N, E, T, F, aggr_host, K, scaler_host, S, long_nodes)) return rc;
   MMA_REQUIRE((gmsg_row_max == nullptr) == (gu_row_max == nullptr) && (!gu_row_max || gU), "the row maxima come as a pair, with gU");
-  if (N == 0 || E == 0) return 0;
+  if (gr_nothing_to_do(N, E, true)) return 0;
   const int D = T * F;
   MMA_REQUIRE(rowptr && src && perm && gout && gmsg && ldg >= D, "NULL argument or pitch too small");
   p.gmsg_rmax = reinterpret_cast<uint32_t*>(gmsg_row_max); p.gu_rmax = reinterpret_cast<uint32_t*>(gu_row_max);
   const bool need_stats = p.need_sq;                              // var / std in the aggregator list (fill_codes)
   MMA_REQUIRE((!p.need_min || amin8) && (!p.need_max || amax8) && (!need_stats || (mean && var)), "saved forward state missing");
   MMA_REQUIRE(!need_stats || (inputs != nullptr) != (U != nullptr && V != nullptr), "var/std backward needs the messages");
-  MMA_REQUIRE(!gU || ldgu >= D, "ldgu=%lld < T*F", (long long)ldgu);
-  MMA_REQUIRE(!(p.need_min || p.need_max || need_stats) || ldsave >= D, "ldsave=%lld < T*F", (long long)ldsave);
+  MMA_REQUIRE(gr_opt_pitch_ok(gU != nullptr, D, ldgu), "ldgu=%lld < T*F", (long long)ldgu);
+  MMA_REQUIRE(gr_opt_pitch_ok(p.need_min || p.need_max || need_stats, D, ldsave), "ldsave=%lld < T*F", (long long)ldsave);
   // saved args the aggregator list does not use are not passed on
   if (int rc = gr_fill_common(p, rowptr, src, perm, U, V, lduv, Z, ldz, by_pos, z_index, inputs, ldi, p.need_min ? amin8 : nullptr,
                               p.need_max ? amax8 : nullptr, p.need_min ? amin_side : nullptr, p.need_max ? amax_side : nullptr, mean, var,
                               ldsave, N, E, T, F, avg_log, avg_lin, drop_mode, drop_thr, seed, seed_dev)) return rc;
   p.gout = gout; p.gmsg = gmsg; p.ldg = ldg; p.gU = gU; p.ldgu = ldgu;
-  const bool v4 = gr_vec4(p) && ldg % 4 == 0 && (reinterpret_cast<uintptr_t>(gmsg) & 15) == 0 &&
-                  (!gU || (ldgu % 4 == 0 && (reinterpret_cast<uintptr_t>(gU) & 15) == 0));
-  return gr_launch<true>(p, E, v4, !need_stats, stream);
+  return gr_launch<true>(p, E, stream);
+}
+
+// The plan of a K3 / K4 call, from what the host ladder reads.  Nothing launches and no pointer is read: every operand the call would
+// have is stood for by an address that is never dereferenced (only its presence and its low four bits reach gr_plan).
+extern "C" int mma_gr_plan(int64_t N, int64_t E, int32_t T, int32_t F, const uint8_t* aggr_host, int32_t K, const uint8_t* scaler_host,
+                           int32_t S, int32_t backward, int64_t lduv, int64_t ldz, int64_t ldi, int64_t ldsave, int64_t ldg, int64_t ldgu,
+                           int32_t has_z, int32_t given, int32_t has_stats, int32_t has_list, int32_t drop_on, int32_t aligned,
+                           int32_t* plan_host) {
+  GrParams p{};
+  static const int32_t stand_in[8] = {0};
+  if (int rc = gr_open(p, N, E, T, F, aggr_host, K, scaler_host, S, has_list ? stand_in : nullptr)) return rc;
+  MMA_REQUIRE(plan_host != nullptr, "NULL plan (%d int32 of host memory)", MMA_GR_PLAN_WORDS);
+  for (int i = 0; i < MMA_GR_PLAN_WORDS; ++i) plan_host[i] = 0;
+  if (gr_nothing_to_do(N, E, backward != 0)) return 0;
+  const int D = T * F;
+  MMA_REQUIRE(lduv >= 0 && ldz >= 0 && ldi >= 0 && ldsave >= 0 && ldg >= 0 && ldgu >= 0, "negative row pitch");
+  MMA_REQUIRE(given ? (lduv == 0 && ldz == 0 && !has_z) : ldi == 0, "give either `inputs` (ldi) or U and V (lduv, ldz)");
+  MMA_REQUIRE(given || lduv > 0, "give either `inputs` (ldi) or U and V (lduv, ldz)");
+  MMA_REQUIRE(!has_stats || ldsave > 0, "saved statistics without ldsave");
+  // then what the entry point of the direction checks of these arguments, with its conditions (K4 does not look at lduv, ldz or ldi)
+  if (backward) {
+    MMA_REQUIRE(ldg >= D, "NULL argument or pitch too small");
+    MMA_REQUIRE(!((p.need_min || p.need_max) && ldsave == 0) && (!p.need_sq || has_stats), "saved forward state missing");
+    MMA_REQUIRE(gr_opt_pitch_ok(ldgu != 0, D, ldgu), "ldgu=%lld < T*F", (long long)ldgu);
+    MMA_REQUIRE(gr_opt_pitch_ok(p.need_min || p.need_max || p.need_sq, D, ldsave), "ldsave=%lld < T*F", (long long)ldsave);
+  } else {
+    MMA_REQUIRE(ldg == 0 && ldgu == 0, "ldg / ldgu belong to the backward");
+    MMA_REQUIRE(gr_msg_pitches_ok(given != 0, has_z != 0, D, ldi, lduv, ldz), "row pitch too small");
+    MMA_REQUIRE(gr_opt_pitch_ok(ldsave != 0, D, ldsave), "ldsave=%lld < T*F", (long long)ldsave);
+  }
+  char* const base = reinterpret_cast<char*>((uintptr_t)(aligned ? 256 : 260));
+  auto at = [&](bool present) -> char* { return present ? base : nullptr; };
+  const bool saved = ldsave > 0;
+  float* const f = reinterpret_cast<float*>(base);
+  p.U = p.V = given ? nullptr : f; p.lduv = lduv; p.Z = has_z ? f : nullptr; p.ldz = ldz;
+  p.inputs = given ? f : nullptr; p.ldi = ldi;
+  p.amin8 = reinterpret_cast<uint8_t*>(at(saved && (!backward || p.need_min))); p.amin_side = reinterpret_cast<int32_t*>(p.amin8);
+  p.amax8 = reinterpret_cast<uint8_t*>(at(saved && (!backward || p.need_max))); p.amax_side = reinterpret_cast<int32_t*>(p.amax8);
+  p.mean = p.var = reinterpret_cast<float*>(at(has_stats != 0)); p.ldsave = ldsave;
+  p.N = (int)N; p.D = D; p.T = T; p.F = F;
+  p.drop.mode = (drop_on && !given) ? MMA_DROP_HASH : MMA_DROP_NONE;
+  if (backward) { p.gout = f; p.gmsg = f; p.ldg = ldg; p.gU = ldgu ? f : nullptr; p.ldgu = ldgu; }
+  else p.out = f;
+  const GrPlan pl = gr_plan(p, E, backward != 0);
+  const int32_t words[MMA_GR_PLAN_WORDS] = {pl.first, pl.vec, pl.nb, pl.needs, pl.lpr_log, pl.chunks, pl.second, pl.lds_bytes};
+  for (int i = 0; i < MMA_GR_PLAN_WORDS; ++i) plan_host[i] = words[i];
+  return 0;
 }

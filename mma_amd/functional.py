@@ -1,6 +1,8 @@
 """autograd wrappers over the C ABI (include/mma_amd.h).  Tensors are plumbing: every FLOP and byte of the
 hot path moves inside libmma_amd.so; torch only owns the memory, the stream and the autograd tape."""
 
+import collections
+import ctypes
 
 import torch
 
@@ -720,6 +722,28 @@ def _gr_call(fn, csr, U, V, Z, by_pos, inputs, extra, N, E, T, F, aggr, scalers,
          1 if by_pos else 0, ptr(z_index), ptr(inputs), D if inputs is not None else 0, *extra, N, E, T, F, host_codes(aggr), len(aggr),
          host_codes(scalers), len(scalers), float(avg_log), float(avg_lin), drop.mode, drop.thr, drop.seed, ptr(drop.seed_tensor),
          stream_ptr())
+
+
+GRPlan = collections.namedtuple("GRPlan", "first vec nb needs lpr_log chunks second lds_bytes")
+GR_FIRST = {0: "none", 1: "flat", 2: "block"}                       # GRPlan.first
+GR_SECOND = {0: "none", 1: "wave", 2: "wave-long", 3: "list"}       # GRPlan.second
+
+
+def gr_plan(N, E, T, F, aggr, scalers, backward=False, lduv=0, ldz=0, ldi=0, ldsave=0, ldg=0, ldgu=0, has_z=False, given=False,
+            has_stats=False, has_list=False, drop_on=False, aligned=True):
+    """The kernels mma_gr_fused_fwd (or, backward=True, mma_gr_fused_bwd) would launch for a call with these arguments (mma_gr_plan, ABI
+    42: host only, nothing launches).  aggr / scalers are code lists; a pitch of 0 means the operand is absent.  The words of the GRPlan
+    are described in include/mma_amd.h, the ladder in DESIGN.md ("The GR launch ladder")."""
+    L = _lib.lib()
+    words = (ctypes.c_int32 * len(GRPlan._fields))()                # MMA_GR_PLAN_WORDS
+    a = (ctypes.c_uint8 * max(len(aggr), 1))(*aggr) if aggr is not None else None
+    s = (ctypes.c_uint8 * max(len(scalers), 1))(*scalers) if scalers is not None else None
+    rc = L.mma_gr_plan(N, E, T, F, a, len(aggr) if aggr is not None else 0, s, len(scalers) if scalers is not None else 0, int(bool(backward)),
+                       lduv, ldz, ldi, ldsave, ldg, ldgu, int(bool(has_z)), int(bool(given)), int(bool(has_stats)), int(bool(has_list)),
+                       int(bool(drop_on)), int(bool(aligned)), words)
+    if rc != 0:
+        raise _lib.MMALibraryError("mma_gr_plan failed (code %d): %s" % (rc, L.mma_last_error().decode()))
+    return GRPlan(*words)
 
 
 class _GRAggregate(torch.autograd.Function):

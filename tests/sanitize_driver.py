@@ -234,8 +234,8 @@ def main():
                         HIST[(name, (lib.mma_last_error() or b"").decode()[:60])] = HIST.get((name, (lib.mma_last_error() or b"").decode()[:60]), 0) + 1
                 continue
             for _, code, pname in params:
-                if code == "H":          # host code list: real memory, valid codes most of the time
-                    n = 8
+                if code == "H":          # host code list: real memory, valid codes most of the time (mma_gr_plan's plan_host: the 8 int32 it writes)
+                    n = 32 if pname == "plan_host" else 8
                     vals = [rng.randrange(0, 6) if rng.random() < 0.9 else rng.randrange(0, 256) for _ in range(n)]
                     arr = (ctypes.c_uint8 * n)(*vals)
                     keep.append(arr)
